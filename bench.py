@@ -18,6 +18,11 @@ N > 1:
   cfg1..cfg3 (mini-batches of small graphs): graphs are the independent units; every rank runs its own
       mini-batch and the parameter gradients are all-reduced (`--mode dp`; also selectable for cfg4): WEAK.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, ...).  `--full` adds
+what takes work or runs of its own beside it: the per-kernel HIP-event table with the roofline and edge-scatter figures,
+the CPU baseline, and at N > 1 the collectives table and the data-parallel leg.  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (the inputs are seeded: two builds can be compared output for output).
 """
 import argparse
 import json
@@ -420,6 +425,28 @@ def matrix_pipe(sq, name, launch_s):
     return round(util, 4), (round(c["mfma_busy"], 4) if c.get("mfma_busy") is not None else None)
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every tensor as d/<name>.npy, float64 as float64 and everything else as float32.  A tensor larger than a
+    quarter of DUMP_BYTES is written as a fixed, seeded sample of its rows (the same rows in every run with the same arguments)."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        a = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        if a.nbytes > DUMP_BYTES // 4:
+            rows = max(1, DUMP_BYTES // 4 // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        total += a.nbytes
+        if total > DUMP_BYTES:
+            raise RuntimeError(f"bench: --dump-outputs would write more than {DUMP_BYTES >> 20} MB (at {name})")
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -443,7 +470,7 @@ def main():
     ap.add_argument("--dtype", choices=["auto", "f32", "bf16"], default="auto",
                     help="MLP operand type: bf16 = bf16 operands / fp32 accumulate (default for cfg3), f32 otherwise")
     ap.add_argument("--cpu-baseline", choices=["auto", "full", "scaled", "none"], default="auto",
-                    help="auto: 'full' at 1 GPU for cfg1..cfg4 (one oracle pass over the whole workload), 'scaled' for cfg5")
+                    help="with --full: auto = 'full' at 1 GPU for cfg1..cfg4 (one oracle pass over the whole workload), 'scaled' for cfg5")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch threads of the CPU baseline (default: all visible CPUs)")
     ap.add_argument("--cache-graph", action="store_true", help="reuse the sorted graph across steps")
@@ -453,6 +480,13 @@ def main():
     ap.add_argument("--train-step", action="store_true",
                     help="time a full training iteration instead (edge_attr augmentation, MSE+MMD loss, Adam: "
                          "fastegnn_amd.train.train_step); the default step is fwd+loss+bwd, the BASELINE metric")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel HIP-event table (from an extra eager pass "
+                         "when the step is replayed as a graph) with the roofline and edge-scatter figures, the CPU baseline "
+                         "(--cpu-baseline), and at N > 1 the collectives table and the data-parallel leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32, float64 "
+                         "stays float64): loc, vloc, loss and the parameter gradients (--train-step: loss and the updated parameters)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -525,8 +559,12 @@ def main():
         if world > 1:
             del frame
             torch.cuda.empty_cache()
-            # second leg of the N > 1 line: graphs as independent units (one frame per rank + gradient all-reduce)
-            dp_frame, dp_target = make_workload(cfg, 143 + rank, dev, args.nodes, args.channels)
+            if args.full:
+                # second leg of the N > 1 line: graphs as independent units (one frame per rank + gradient all-reduce)
+                dp_frame, dp_target = make_workload(cfg, 143 + rank, dev, args.nodes, args.channels)
+
+    # --dump-outputs: detached outputs of the latest step (a captured graph's replays write into the ones the capture made)
+    last = {}
 
     def step():
         if args.train_step:   # utils/train.py:30-170 on device (single-GPU only)
@@ -541,12 +579,14 @@ def main():
             loss = (loc - tgt_local).pow(2).sum() / (3 * N) + 0.01 * vloc.pow(2).mean()
             loss.backward()
             allreduce_gradients(params)
-            return loss
-        loc, vloc = model(**frame)
-        loss = loss_fn(loc, vloc, target)
-        loss.backward()
-        if world > 1:   # data-parallel gradient exchange (one flat bucket, 2.2 MB, RCCL over xGMI)
-            allreduce_gradients(params)
+        else:
+            loc, vloc = model(**frame)
+            loss = loss_fn(loc, vloc, target)
+            loss.backward()
+            if world > 1:   # data-parallel gradient exchange (one flat bucket, 2.2 MB, RCCL over xGMI)
+                allreduce_gradients(params)
+        if args.dump_outputs:
+            last.update(loc=loc.detach(), vloc=vloc.detach())
         return loss
 
     def sync():
@@ -560,19 +600,21 @@ def main():
     # ~50 GB, so it stays eager
     use_graph = args.hipgraph == "on" or (args.hipgraph == "auto" and world == 1 and not sharded and not args.train_step
                                           and (args.nodes or cfg["nodes"]) <= 200000)
-    # the per-kernel HIP-event profiler is on during warm-up too, so that its event pool exists
+    # --full: the per-kernel HIP-event profiler is on during warm-up too, so that its event pool exists
     # before the timed region (hipEventCreate is slow on a cold driver)
-    K.lib().fastegnn_profile_enable(1)
+    if args.full:
+        K.lib().fastegnn_profile_enable(1)
     # two extra untimed steps ahead of the W warm-up steps: on a freshly booted box the first pass still pages
     # the Python / torch / HIP code in from the image, which showed up as sporadic 100 ms host stalls
     for _ in range(2 + max(args.warmup, 1)):
         step()
     sync()
-    K.profile_collect()
+    if args.full:
+        K.profile_collect()
     prof_steps = args.steps
     prof_taken = False
     eager_ms = None
-    if use_graph:
+    if use_graph and args.full:
         # per-kernel durations from an eager pass (events cannot be timed inside a captured graph), then the step is
         # captured once and the timed region replays it
         prof_steps = min(args.steps, 20)
@@ -591,11 +633,13 @@ def main():
             step()
         sync()
         eager_ms = min(eager_ms, (time.perf_counter() - t0) / prof_steps * 1e3)
+    if use_graph:
         gstream = torch.cuda.Stream(dev)
         gstream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(gstream):
             step()                                   # allocator warm-up on the capture stream
         torch.cuda.current_stream(dev).wait_stream(gstream)
+        last.clear()                                 # nothing of an eager step is held across the capture
         hgraph = torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(hgraph, stream=gstream):
@@ -614,7 +658,7 @@ def main():
         sync()
         dt = time.perf_counter() - t0
     else:
-        if sharded:
+        if sharded and args.full:
             stats = CommStats()
             smodel.stats = stats
         t0 = time.perf_counter()
@@ -628,13 +672,22 @@ def main():
             done.append(ev)
         sync()
         dt = time.perf_counter() - t0
-        if not prof_taken:   # (after a failed graph capture the per-kernel table of the eager pre-pass is kept)
+        if args.full and not prof_taken:   # (after a failed graph capture the per-kernel table of the eager pre-pass is kept)
             K.lib().fastegnn_profile_enable(0)
             prof = K.profile_collect()
     dt = max_over_ranks(dt, dev)
 
+    if args.dump_outputs and rank == 0:
+        if args.train_step:
+            arrays = {"loss": loss}
+            arrays.update({"param." + n: p for n, p in model.named_parameters()})
+        else:
+            arrays = {"loc": last["loc"], "vloc": last["vloc"], "loss": loss}
+            arrays.update({"grad." + n: p.grad for n, p in model.named_parameters() if p.grad is not None})
+        dump_outputs(args.dump_outputs, arrays)
+
     dp_leg = None
-    if sharded and world > 1:
+    if sharded and world > 1 and args.full:
         # the same job as data-parallel replicas (weak scaling): every rank its own frame, no data-path collective,
         # one flat gradient all-reduce -- reported beside the partitioned number, same steps / warm-up / barriers
         def dp_step():
@@ -668,77 +721,79 @@ def main():
         value = units_per_step * args.steps / dt
         # kernel model of what THIS rank ran (sharded: its 1/world share of the rows and edges)
         kN, kE = (shard["plan"].nloc, shard["edge_index"].size(1)) if sharded else (N, E)
-        phased = "virt_bwd_kernel" in prof and "virt_bwd_gv_kernel" not in prof      # which form of the virtual backward ran
-        km = kernel_model(kN, kE, B, C, L, gravity=cfg["gravity"] is not None, phased=phased)
-        ob = operand_bytes(kN, kE, B, C, gravity=cfg["gravity"] is not None)
-        kernels = {}
-        rfree = recompute_free_units(kN, kE, B, C, phased=phased)
-        sq, sq_file = latest_sq_counters() if (args.config == "cfg4" and not sharded and dtype != "bf16") else ({}, None)
-        sq_meta = sq.get("_meta", {}) if sq else {}
-        for name, (ms, cnt) in prof.items():
-            per_step = ms / prof_steps
-            launch_s = ms / cnt * 1e-3
-            ent = {"ms_per_step": round(per_step, 4), "launches_per_step": cnt / prof_steps,
-                   "avg_launch_ms": round(ms / cnt, 5)}
-            if name in km:
-                fl, by = km[name]
-                # fp32-EQUIVALENT rate: algorithmic 64x64 products per launch (recomputed ones included) x 8192 FLOP / launch duration.
-                # The products run as 16-bit MFMAs (f16x2 / bf16x3 splits): this is not a fraction of any pipe's peak and may exceed
-                # the 157.3 TFLOP/s of the fp32-input MFMA; what the matrix pipe did is `matrix_pipe_util`
-                ent["fp32_equivalent_tflops"] = round(fl / launch_s / 1e12, 3)
-                if by is not None:
-                    ent["gbs"] = round(by / launch_s / 1e9, 1)                   # SURVEY 8d algorithmic bytes per launch
-                util, busy = matrix_pipe(sq, name, launch_s)
-                if util is not None:
-                    ent["matrix_pipe_util"] = util
-                    ent["mfma_busy"] = busy
-            if name == "edge_col_reduce_kernel":
-                ent["operand_gbs"] = round(ob[name] / launch_s / 1e9, 1)
-            if name == "wgrad_tn_kernel":
-                if phased:   # ONE launch per layer: the layer-wide batch (dW3c goes through the phased kernel's own slabs + wgrad_reduce)
-                    ent["operand_gbs"] = round(ob["wgrad_tn_kernel[layer batch]"] / launch_s / 1e9, 1)
-                else:        # tile-major form: two launches per layer, the second is the per-channel node_mlp.0 job over v
-                    tot = ob["wgrad_tn_kernel[layer batch]"] + ob["wgrad_tn_kernel[v job]"]
-                    ent["operand_gbs"] = round(tot / (2 * launch_s) / 1e9, 1)
-            kernels[name] = ent
-        dom = max((n for n in kernels if n in km), key=lambda n: kernels[n]["ms_per_step"])
-        fl, by = km[dom]
-        fl_alg = rfree.get(dom, fl)            # without the forward products a backward kernel recomputes (bwd = 2 x fwd)
-        launch_s = kernels[dom]["avg_launch_ms"] * 1e-3
-        peak_mfma = PEAK_MFMA_BF16_TFLOPS if dtype == "bf16" else PEAK_MFMA_F32_TFLOPS
-        t_mfma = fl / (peak_mfma * 1e12)
-        t_hbm = (by or 0) / (PEAK_HBM_GBS * 1e9)
-        tr, tr_file = latest_traffic()
-        traffic = tr.get(dom, {}).get("hbm_bytes_per_launch") if (args.config == "cfg4" and not sharded) else None
-        if t_mfma >= t_hbm:
-            # achieved = ALGORITHMIC FLOPs (the transposed products and the weight-gradient contractions of a backward
-            # kernel, NOT its recomputed forward products) per launch / the launch duration measured in this run; peak = the dense
-            # MFMA peak of the arithmetic type (fp32: 157.3 TFLOP/s).  Recomputation and the 16-bit split products therefore show up
-            # as lost efficiency, never as achieved work.
-            ach = fl_alg / launch_s / 1e12
-            # `frac` is a FP32-EQUIVALENT figure (algorithmic fp32 FLOPs over the fp32-input MFMA peak), NOT the utilisation of the pipe the
-            # kernel runs on: that is `matrix_pipe_util` right beside it
-            roof = {"kernel": dom, "bound": "mfma", "achieved": round(ach, 3), "peak": peak_mfma,
-                    "unit": "TFLOP/s", "frac": round(ach / peak_mfma, 4), "frac_is": "fp32-equivalent algorithmic FLOPs / fp32-input MFMA peak; "
-                    "the 16-bit matrix pipe's own utilisation is matrix_pipe_util", "traffic": traffic,
-                    "algorithmic_flops_per_launch": fl_alg, "executed_product_flops_per_launch": fl}
-            util, busy = matrix_pipe(sq, dom, launch_s)
-            roof["matrix_pipe_util"] = util      # 16-bit MFMA FLOPs the counters saw / duration / 2.5 PFLOP/s dense
-            roof["mfma_busy"] = busy             # SQ_VALU_MFMA_BUSY_CYCLES / the SIMDs' time, from the tracked capture
-            roof["counters_source"] = (f"profiles/{sq_file}: rocprofv3 --pmc passes (tools/gpu_sq.sh) of commit "
-                                       f"{sq_meta.get('commit', '?')}, not of this run; durations are this run's") if util is not None else None
-        else:
-            roof = {"kernel": dom, "bound": "hbm", "achieved": kernels[dom]["gbs"], "peak": PEAK_HBM_GBS,
-                    "unit": "GB/s", "frac": round(kernels[dom]["gbs"] / PEAK_HBM_GBS, 4), "traffic": traffic}
-        roof["traffic_source"] = (f"profiles/{tr_file}: rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE) of the commit named in "
-                                  f"that file, not of this run") if traffic is not None else None
-        es = kernels.get("edge_fwd_kernel")
-        edge_scatter = None
-        if es:
-            edge_scatter = {"kernel": "edge_fwd_kernel", "algorithmic_bytes_per_launch": 280 * kE + 540 * kN,
-                            "achieved_GBs": es["gbs"], "frac_of_hbm_peak": round(es["gbs"] / PEAK_HBM_GBS, 4),
-                            "fp32_equivalent_tflops": es["fp32_equivalent_tflops"],
-                            "matrix_pipe_util": es.get("matrix_pipe_util"), "mfma_busy": es.get("mfma_busy")}
+        roof = edge_scatter = kernels = None
+        if args.full:
+            phased = "virt_bwd_kernel" in prof and "virt_bwd_gv_kernel" not in prof      # which form of the virtual backward ran
+            km = kernel_model(kN, kE, B, C, L, gravity=cfg["gravity"] is not None, phased=phased)
+            ob = operand_bytes(kN, kE, B, C, gravity=cfg["gravity"] is not None)
+            kernels = {}
+            rfree = recompute_free_units(kN, kE, B, C, phased=phased)
+            sq, sq_file = latest_sq_counters() if (args.config == "cfg4" and not sharded and dtype != "bf16") else ({}, None)
+            sq_meta = sq.get("_meta", {}) if sq else {}
+            for name, (ms, cnt) in prof.items():
+                per_step = ms / prof_steps
+                launch_s = ms / cnt * 1e-3
+                ent = {"ms_per_step": round(per_step, 4), "launches_per_step": cnt / prof_steps,
+                       "avg_launch_ms": round(ms / cnt, 5)}
+                if name in km:
+                    fl, by = km[name]
+                    # fp32-EQUIVALENT rate: algorithmic 64x64 products per launch (recomputed ones included) x 8192 FLOP / launch duration.
+                    # The products run as 16-bit MFMAs (f16x2 / bf16x3 splits): this is not a fraction of any pipe's peak and may exceed
+                    # the 157.3 TFLOP/s of the fp32-input MFMA; what the matrix pipe did is `matrix_pipe_util`
+                    ent["fp32_equivalent_tflops"] = round(fl / launch_s / 1e12, 3)
+                    if by is not None:
+                        ent["gbs"] = round(by / launch_s / 1e9, 1)                   # SURVEY 8d algorithmic bytes per launch
+                    util, busy = matrix_pipe(sq, name, launch_s)
+                    if util is not None:
+                        ent["matrix_pipe_util"] = util
+                        ent["mfma_busy"] = busy
+                if name == "edge_col_reduce_kernel":
+                    ent["operand_gbs"] = round(ob[name] / launch_s / 1e9, 1)
+                if name == "wgrad_tn_kernel":
+                    if phased:   # ONE launch per layer: the layer-wide batch (dW3c goes through the phased kernel's own slabs + wgrad_reduce)
+                        ent["operand_gbs"] = round(ob["wgrad_tn_kernel[layer batch]"] / launch_s / 1e9, 1)
+                    else:        # tile-major form: two launches per layer, the second is the per-channel node_mlp.0 job over v
+                        tot = ob["wgrad_tn_kernel[layer batch]"] + ob["wgrad_tn_kernel[v job]"]
+                        ent["operand_gbs"] = round(tot / (2 * launch_s) / 1e9, 1)
+                kernels[name] = ent
+            dom = max((n for n in kernels if n in km), key=lambda n: kernels[n]["ms_per_step"])
+            fl, by = km[dom]
+            fl_alg = rfree.get(dom, fl)            # without the forward products a backward kernel recomputes (bwd = 2 x fwd)
+            launch_s = kernels[dom]["avg_launch_ms"] * 1e-3
+            peak_mfma = PEAK_MFMA_BF16_TFLOPS if dtype == "bf16" else PEAK_MFMA_F32_TFLOPS
+            t_mfma = fl / (peak_mfma * 1e12)
+            t_hbm = (by or 0) / (PEAK_HBM_GBS * 1e9)
+            tr, tr_file = latest_traffic()
+            traffic = tr.get(dom, {}).get("hbm_bytes_per_launch") if (args.config == "cfg4" and not sharded) else None
+            if t_mfma >= t_hbm:
+                # achieved = ALGORITHMIC FLOPs (the transposed products and the weight-gradient contractions of a backward
+                # kernel, NOT its recomputed forward products) per launch / the launch duration measured in this run; peak = the dense
+                # MFMA peak of the arithmetic type (fp32: 157.3 TFLOP/s).  Recomputation and the 16-bit split products therefore show up
+                # as lost efficiency, never as achieved work.
+                ach = fl_alg / launch_s / 1e12
+                # `frac` is a FP32-EQUIVALENT figure (algorithmic fp32 FLOPs over the fp32-input MFMA peak), NOT the utilisation of the pipe the
+                # kernel runs on: that is `matrix_pipe_util` right beside it
+                roof = {"kernel": dom, "bound": "mfma", "achieved": round(ach, 3), "peak": peak_mfma,
+                        "unit": "TFLOP/s", "frac": round(ach / peak_mfma, 4), "frac_is": "fp32-equivalent algorithmic FLOPs / fp32-input MFMA peak; "
+                        "the 16-bit matrix pipe's own utilisation is matrix_pipe_util", "traffic": traffic,
+                        "algorithmic_flops_per_launch": fl_alg, "executed_product_flops_per_launch": fl}
+                util, busy = matrix_pipe(sq, dom, launch_s)
+                roof["matrix_pipe_util"] = util      # 16-bit MFMA FLOPs the counters saw / duration / 2.5 PFLOP/s dense
+                roof["mfma_busy"] = busy             # SQ_VALU_MFMA_BUSY_CYCLES / the SIMDs' time, from the tracked capture
+                roof["counters_source"] = (f"profiles/{sq_file}: rocprofv3 --pmc passes (tools/gpu_sq.sh) of commit "
+                                           f"{sq_meta.get('commit', '?')}, not of this run; durations are this run's") if util is not None else None
+            else:
+                roof = {"kernel": dom, "bound": "hbm", "achieved": kernels[dom]["gbs"], "peak": PEAK_HBM_GBS,
+                        "unit": "GB/s", "frac": round(kernels[dom]["gbs"] / PEAK_HBM_GBS, 4), "traffic": traffic}
+            roof["traffic_source"] = (f"profiles/{tr_file}: rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE) of the commit named in "
+                                      f"that file, not of this run") if traffic is not None else None
+            es = kernels.get("edge_fwd_kernel")
+            edge_scatter = None
+            if es:
+                edge_scatter = {"kernel": "edge_fwd_kernel", "algorithmic_bytes_per_launch": 280 * kE + 540 * kN,
+                                "achieved_GBs": es["gbs"], "frac_of_hbm_peak": round(es["gbs"] / PEAK_HBM_GBS, 4),
+                                "fp32_equivalent_tflops": es["fp32_equivalent_tflops"],
+                                "matrix_pipe_util": es.get("matrix_pipe_util"), "mfma_busy": es.get("mfma_busy")}
         if sharded:
             par = f"row-owner sharding of ONE batch over {world} GPU(s) (fastegnn_amd/sharded.py), strong scaling"
         elif world > 1:
@@ -757,19 +812,23 @@ def main():
                                    + ("cached" if args.cache_graph else "inside the step"),
                        "name": args.config, "nodes": N, "edges": E, "graphs_per_batch": B, "virtual_channels": C, "layers": L,
                        "graphs_per_step": units_per_step, "parallelism": par, "loss": float(loss.detach()),
-                       "launch": ("whole step replayed as one captured HIP graph; per-kernel durations from an eager pass of "
-                                  f"{prof_steps} steps before the capture") if use_graph else "eager launches"},
+                       "launch": ("whole step replayed as one captured HIP graph" + ("; per-kernel durations from an eager pass of "
+                                  f"{prof_steps} steps before the capture" if prof_taken else "")) if use_graph else "eager launches"},
             "value_per_gpu": round(value / world, 4),
             "peak_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2),
             "roofline": roof,
             "edge_scatter": edge_scatter,
             "kernels": kernels,
         }
+        if not args.full:   # the eager-launch rate and the per-kernel / roofline figures come from --full's profiled pass
+            for k in ("eager_ms_per_step", "roofline", "edge_scatter", "kernels"):
+                del out[k]
         if stats is not None:
             out["collectives"] = stats.summary(args.steps)
         if sharded:
             pl = shard["plan"]
-            out["launches_per_step"] = sum(v["launches_per_step"] for v in kernels.values())
+            if kernels is not None:
+                out["launches_per_step"] = sum(v["launches_per_step"] for v in kernels.values())
             out["shard"] = {"rows": pl.nloc, "edges": kE, "edge_stage_launch_ranges": [
                 {"first_row": r0, "rows": n, "waits_for_halo": bool(h)} for r0, n, h in pl.parts],
                 "transport": os.environ.get("FASTEGNN_COMM", "torch"),
@@ -786,7 +845,7 @@ def main():
                                                              else "asynchronous, waited for at the first consumer")}
         if dp_leg is not None:
             out["data_parallel_leg"] = dp_leg
-        cb = "none" if args.no_cpu_baseline else args.cpu_baseline
+        cb = "none" if (args.no_cpu_baseline or not args.full) else args.cpu_baseline
         if cb == "auto":
             cb = "none" if world > 1 else ("scaled" if args.config == "cfg5" else "full")
         if cb != "none" and world == 1:

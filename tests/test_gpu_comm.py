@@ -84,12 +84,12 @@ def test_halo_pack_and_unpack_kernels(comm):
 def test_bench_two_ranks_over_gloo_prints_one_json_line():
     """`python bench.py --gpus 2` as the driver launches it for N > 1, with the two ranks sharing this box's one GPU over
     gloo (FASTEGNN_BENCH_BACKEND=gloo): fresh child processes, the partitioned frame with the Morton-ordered halo
-    exchange, the data-parallel leg, ONE JSON line on stdout."""
+    exchange, the data-parallel leg and the collectives table (--full), ONE JSON line on stdout."""
     env = dict(os.environ, FASTEGNN_BENCH_BACKEND="gloo", FASTEGNN_BENCH_TIMEOUT="600")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--nodes", "20000"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          "--nodes", "20000", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -5,7 +5,7 @@
 O=gpurun_out/virt_pre_mfma; mkdir -p $O
 cp fastegnn_amd/libfastegnn_hip.so $O/default.so
 run() {  # tag
-  python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '{"metric"' > $O/$1.json
+  python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '{"metric"' > $O/$1.json
   python - <<PY
 import json
 d = json.load(open("$O/$1.json"))
@@ -15,11 +15,11 @@ print("$1", "ms/step", d["ms_per_step"], " ".join(f"{n.replace('_kernel','')}={v
 PY
 }
 for rep in 1 2; do
-  cp gpurun_alt_valu.so fastegnn_amd/libfastegnn_hip.so; run valu_$rep
+  cp alt_valu.so fastegnn_amd/libfastegnn_hip.so; run valu_$rep
   cp $O/default.so fastegnn_amd/libfastegnn_hip.so; run mfma_$rep
 done
-cp gpurun_alt_valu.so fastegnn_amd/libfastegnn_hip.so; python bench.py --config cfg3 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '{"metric"' > $O/cfg3_valu.json
-cp $O/default.so fastegnn_amd/libfastegnn_hip.so; python bench.py --config cfg3 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '{"metric"' > $O/cfg3_mfma.json
+cp alt_valu.so fastegnn_amd/libfastegnn_hip.so; python bench.py --full --config cfg3 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '{"metric"' > $O/cfg3_valu.json
+cp $O/default.so fastegnn_amd/libfastegnn_hip.so; python bench.py --full --config cfg3 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '{"metric"' > $O/cfg3_mfma.json
 python - <<'PY'
 import json
 for t in ("valu", "mfma"):

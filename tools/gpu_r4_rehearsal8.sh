@@ -5,7 +5,7 @@ O=gpurun_out/reh8; mkdir -p $O
 export FASTEGNN_BENCH_BACKEND=gloo
 for n in 4 8; do
   timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29550 + n)) \
-    bench.py --gpus $n --steps 3 --warmup 1 --no-cpu-baseline > $O/r$n.json 2> $O/r$n.err
+    bench.py --full --gpus $n --steps 3 --warmup 1 --no-cpu-baseline > $O/r$n.json 2> $O/r$n.err
   echo "N=$n exit $?"
   python - <<PY
 import json

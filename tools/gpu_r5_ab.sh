@@ -8,7 +8,7 @@ for extra in "$@"; do
   envv=""
   case "$extra" in ENV:*) envv="${extra#ENV:}"; extra="";; esac
   ( cd fastegnn_amd/csrc && ls *.o | grep -v "^wide" | xargs rm -f && make -j16 ../libfastegnn_hip.so EXTRA="$extra" > /dev/null 2>&1 ) || { echo "build failed: $extra"; continue; }
-  env $envv timeout 300 python bench.py --steps 40 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} 2>$O/v$i.err | grep '{"metric"' > $O/v$i.json || tail -3 $O/v$i.err
+  env $envv timeout 300 python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} 2>$O/v$i.err | grep '{"metric"' > $O/v$i.json || tail -3 $O/v$i.err
   python - "$extra$envv" $O/v$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

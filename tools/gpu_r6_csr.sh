@@ -14,10 +14,10 @@ for form in default radix default radix; do
   [ $form = radix ] && export FASTEGNN_CSR_SORT=radix || unset FASTEGNN_CSR_SORT
   echo "== $form" | tee -a $O/ab.txt
   for w in 8 4; do
-    FASTEGNN_COMM=abi timeout 300 python bench.py --emulate-world $w --hipgraph on --steps 50 --warmup 3 --no-cpu-baseline > $O/emu${w}_$form.json 2> $O/emu${w}_$form.err; echo -n "emu$w (replayed):" | tee -a $O/ab.txt; line $O/emu${w}_$form.json | tee -a $O/ab.txt
+    FASTEGNN_COMM=abi timeout 300 python bench.py --full --emulate-world $w --hipgraph on --steps 50 --warmup 3 --no-cpu-baseline > $O/emu${w}_$form.json 2> $O/emu${w}_$form.err; echo -n "emu$w (replayed):" | tee -a $O/ab.txt; line $O/emu${w}_$form.json | tee -a $O/ab.txt
   done
-  timeout 300 python bench.py --config cfg1 --steps 200 --warmup 5 --no-cpu-baseline > $O/cfg1_$form.json 2> $O/cfg1_$form.err; echo -n "cfg1:" | tee -a $O/ab.txt; line $O/cfg1_$form.json | tee -a $O/ab.txt
-  timeout 300 python bench.py --steps 100 --warmup 5 --no-cpu-baseline > $O/cfg4_$form.json 2> $O/cfg4_$form.err; echo -n "cfg4:" | tee -a $O/ab.txt; line $O/cfg4_$form.json | tee -a $O/ab.txt
+  timeout 300 python bench.py --full --config cfg1 --steps 200 --warmup 5 --no-cpu-baseline > $O/cfg1_$form.json 2> $O/cfg1_$form.err; echo -n "cfg1:" | tee -a $O/ab.txt; line $O/cfg1_$form.json | tee -a $O/ab.txt
+  timeout 300 python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline > $O/cfg4_$form.json 2> $O/cfg4_$form.err; echo -n "cfg4:" | tee -a $O/ab.txt; line $O/cfg4_$form.json | tee -a $O/ab.txt
 done
 unset FASTEGNN_CSR_SORT
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_sharded.py tests/test_gpu_graphs.py -m gpu -q -x -p no:cacheprovider 2>&1 | tail -2 | tee -a $O/tests.txt

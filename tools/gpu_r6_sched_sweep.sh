@@ -7,7 +7,7 @@ i=0
 for sch in "$@"; do
   [ "$sch" = "-" ] && sch=""
   ( cd fastegnn_amd/csrc && rm -f $FILES && make -j16 $FILES "SCHED=$sch" > $O/build$i.log 2>&1 && make ../libfastegnn_hip.so > $O/build$i.log 2>&1 ) || { echo "build failed: $sch"; tail -2 $O/build$i.log; i=$((i+1)); continue; }
-  timeout 300 python bench.py --steps 40 --warmup 3 --no-cpu-baseline 2>$O/v$i.err | grep '{"metric"' > $O/v$i.json || tail -3 $O/v$i.err
+  timeout 300 python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline 2>$O/v$i.err | grep '{"metric"' > $O/v$i.json || tail -3 $O/v$i.err
   python - "$sch" $O/v$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2])); k = d["kernels"]

@@ -3,7 +3,7 @@
 O=gpurun_out/r06verify; mkdir -p $O
 python -m pytest tests -m gpu -q 2>&1 | tail -6 > $O/gpu_suite.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 > $O/smoke.txt
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 { echo "# pytest -m gpu on the round-6 final tree, one MI355X box:"; cat $O/gpu_suite.txt; echo "# __graft_entry__.smoke():"; cat $O/smoke.txt; echo "# python bench.py (default: cfg4, 1 GPU):"; python - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r06verify/bench.json") if l.startswith("{")][0])

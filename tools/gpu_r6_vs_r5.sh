@@ -7,5 +7,5 @@ import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); k
 print('[$1] ms/step', d['ms_per_step'], 'eager', d['eager_ms_per_step'], 'graphs/s', d['value'], ' '.join('%s %.3f' % (n.replace('_kernel',''), k[n]['ms_per_step']) for n in ('edge_fwd_kernel','virt_fwd_kernel','edge_bwd_kernel','virt_bwd_kernel')))"; }
 for rep in 1 2 3; do
   ( cd build/r05tree && python bench.py --steps 40 --warmup 3 --no-cpu-baseline 2>/dev/null ) | line "round 5 (45e3900)"
-  python bench.py --steps 40 --warmup 3 --no-cpu-baseline 2>/dev/null | line "round 6 (this tree)"
+  python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline 2>/dev/null | line "round 6 (this tree)"
 done
