@@ -35,7 +35,7 @@ def lib_path(act: bool = False, wide: bool = False) -> str:
 
 LIB_PATH = lib_path(False, bool(WIDE_RANGE))   # the library the stage-independent helpers (CSR, graphs, training step, comm) use
 
-ABI_VERSION = 107   # FASTEGNN_ABI_VERSION of include/fastegnn_hip.h this mirror was written against
+ABI_VERSION = 108   # FASTEGNN_ABI_VERSION of include/fastegnn_hip.h this mirror was written against
 H = 64
 QX_LD = 68
 FEATW = 8
@@ -164,6 +164,8 @@ def lib(act: bool = False, wide=None):
     L.fastegnn_loss_mse_mmd.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp, _vp]
     L.fastegnn_adam_step.argtypes = [_vp, _vp, _vp, _vp, C.POINTER(C.c_int64), _i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_float, _vp]
+    L.fastegnn_adam_step_v2.argtypes = [_vp, _vp, _vp, _vp, C.POINTER(C.c_int64), _i32, C.POINTER(_i32), C.c_double, C.c_double,
+                                        C.c_double, C.c_double, C.c_double, _vp]
     L.fastegnn_radius_graph_ws_bytes.restype = C.c_size_t
     L.fastegnn_radius_graph_ws_bytes.argtypes = [_i32]
     L.fastegnn_radius_graph_count.argtypes = [_vp, _i32, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]
@@ -250,7 +252,7 @@ EXPORTED = STAGE_FUNCS + [
     "fastegnn_build_csr", "fastegnn_pad_params", "fastegnn_generic_activations", "fastegnn_f16_operands", "fastegnn_check_finite", "fastegnn_host_words_alloc", "fastegnn_host_words_free", "fastegnn_zero_if_flagged", "fastegnn_spin_timeouts", "fastegnn_permute_rows", "fastegnn_build_batch", "fastegnn_embed_forward",
     "fastegnn_embed_backward", "fastegnn_virtual_init", "fastegnn_virtual_init_backward",
     "fastegnn_layer_forward", "fastegnn_layer_backward", "fastegnn_selftest_gemm", "fastegnn_selftest_rm", "fastegnn_selftest_jreduce", "fastegnn_selftest_lane_sums", "fastegnn_selftest_wgrad", "fastegnn_selftest_wgrad_plan", "fastegnn_selftest_wgrad_guard", "fastegnn_selftest_stream", "fastegnn_selftest_chain", "fastegnn_selftest_chain_bf3",
-    "fastegnn_augment_edge_attr", "fastegnn_loss_mse_mmd", "fastegnn_adam_step",
+    "fastegnn_augment_edge_attr", "fastegnn_loss_mse_mmd", "fastegnn_adam_step", "fastegnn_adam_step_v2",
     "fastegnn_radius_graph_ws_bytes", "fastegnn_radius_graph_count", "fastegnn_radius_graph_fill",
     "fastegnn_cutoff_tmp_bytes", "fastegnn_cutoff_edges", "fastegnn_nbody_cutoff_edges",
     "fastegnn_profile_enable", "fastegnn_profile_kernels", "fastegnn_profile_name", "fastegnn_profile_collect",

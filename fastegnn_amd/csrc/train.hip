@@ -2,6 +2,8 @@
 // harness that bracket the hot path in utils/train.py -- edge_attr augmentation (:41-43), MSE + MMD loss
 // with its gradient (:104-165, kernel() :17-20) and Adam (main_nbody.py:137) -- so that one training
 // iteration never leaves the GPU.
+#include <vector>
+
 #include "kernels.h"
 
 namespace fe {
@@ -92,28 +94,31 @@ __global__ __launch_bounds__(256) void loss_mmd_kernel(const float *pred, const 
   }
 }
 
-// torch.optim.Adam (no amsgrad; weight decay folded into the gradient), up to 24 tensors per launch
+// torch.optim.Adam (no amsgrad; weight decay folded into the gradient), up to 24 tensors per launch.  Each tensor carries its
+// own bias correction: torch keeps state['step'] per parameter and advances it only on steps where the parameter has a .grad
 constexpr int ADAM_MAX = 24;
 struct AdamArgs {
   float *p[ADAM_MAX], *m[ADAM_MAX], *v[ADAM_MAX];
   const float *g[ADAM_MAX];
   long n[ADAM_MAX];
+  float lr_t[ADAM_MAX], inv_bc2_sqrt[ADAM_MAX];   // lr / (1 - b1^step), 1 / sqrt(1 - b2^step) of the tensor's own step
   int count;
-  float lr_t, b1, b2, inv_bc2_sqrt, eps, wd;
+  float b1, b2, omb1, omb2, eps, wd;   // omb = 1 - beta, rounded once from double (1.f - 0.999f is 1.3e-5 off 0.001)
 };
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   const int t = blockIdx.y;
   if (t >= a.count) return;
   float *p = a.p[t], *m = a.m[t], *v = a.v[t];
   const float *g = a.g[t];
-  if (!g) return;   // torch.optim.Adam skips parameters whose .grad is None: no decay, no moment update
+  if (!g) return;   // torch.optim.Adam skips parameters whose .grad is None: no decay, no moment update, no step
+  const float lr_t = a.lr_t[t], inv_bc2_sqrt = a.inv_bc2_sqrt[t];
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n[t]; i += (long)gridDim.x * 256) {
     const float gi = g[i] + a.wd * p[i];
-    const float mi = a.b1 * m[i] + (1.f - a.b1) * gi;
-    const float vi = a.b2 * v[i] + (1.f - a.b2) * gi * gi;
+    const float mi = a.b1 * m[i] + a.omb1 * gi;
+    const float vi = a.b2 * v[i] + a.omb2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
-    p[i] -= a.lr_t * mi / (sqrtf(vi) * a.inv_bc2_sqrt + a.eps);
+    p[i] -= lr_t * mi / (sqrtf(vi) * inv_bc2_sqrt + a.eps);
   }
 }
 
@@ -150,12 +155,13 @@ int fastegnn_loss_mse_mmd(const float *loc_pred, const float *loc_t, const float
   return check_launch("loss_mse_mmd");
 }
 
-int fastegnn_adam_step(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
-                       const int64_t *numel, int32_t n_tensors, int32_t step, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, void *stream) {
-  FE_REQUIRE(params && grads && exp_avg && exp_avg_sq && numel && step >= 1, "adam_step: bad argument");
+int fastegnn_adam_step_v2(float *const *params, const float *const *grads, float *const *exp_avg,
+                          float *const *exp_avg_sq, const int64_t *numel, int32_t n_tensors, const int32_t *steps,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, void *stream) {
+  FE_REQUIRE(params && grads && exp_avg && exp_avg_sq && numel && steps && n_tensors >= 0, "adam_step: bad argument");
+  for (int t = 0; t < n_tensors; ++t)
+    FE_REQUIRE(!grads[t] || steps[t] >= 1, "adam_step: a tensor with a gradient needs step >= 1");
   hipStream_t st = (hipStream_t)stream;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   for (int base = 0; base < n_tensors; base += ADAM_MAX) {
     AdamArgs a;
     a.count = n_tensors - base < ADAM_MAX ? n_tensors - base : ADAM_MAX;
@@ -163,16 +169,30 @@ int fastegnn_adam_step(float *const *params, const float *const *grads, float *c
     for (int t = 0; t < a.count; ++t) {
       a.p[t] = params[base + t]; a.g[t] = grads[base + t]; a.m[t] = exp_avg[base + t]; a.v[t] = exp_avg_sq[base + t];
       a.n[t] = numel[base + t];
+      const int step = a.g[t] ? steps[base + t] : 1;   // a skipped tensor's count is not read
+      const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
+      a.lr_t[t] = (float)(lr / bc1);
+      a.inv_bc2_sqrt[t] = (float)(1.0 / sqrt(bc2));
       if (a.n[t] > nmax) nmax = a.n[t];
     }
-    a.lr_t = (float)(lr / bc1); a.b1 = beta1; a.b2 = beta2; a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2)); a.eps = eps;
-    a.wd = weight_decay;
+    a.b1 = (float)beta1; a.b2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps; a.wd = (float)weight_decay;
     int gx = cdiv(nmax, 256 * 4);
     if (gx > 64) gx = 64;
     if (gx < 1) gx = 1;
     hipLaunchKernelGGL(adam_kernel, dim3(gx, a.count), dim3(256), 0, st, a);
   }
   return check_launch("adam_kernel");
+}
+
+// every tensor at the same step: the form of ABI revisions up to 107
+int fastegnn_adam_step(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                       const int64_t *numel, int32_t n_tensors, int32_t step, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, void *stream) {
+  FE_REQUIRE(step >= 1 && n_tensors >= 0, "adam_step: bad argument");
+  std::vector<int32_t> steps((size_t)n_tensors, step);
+  return fastegnn_adam_step_v2(params, grads, exp_avg, exp_avg_sq, numel, n_tensors, steps.data(), lr, beta1, beta2,
+                               eps, weight_decay, stream);
 }
 
 }  // extern "C"

@@ -65,8 +65,11 @@ class FusedAdam:
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = [torch.zeros_like(p) for p in self.params]
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
-        self.step_count = 0
+        self.step_count = 0                    # calls of step()
         n = len(self.params)
+        # torch.optim.Adam's state['step'] of each parameter: advanced only on the steps where it has a .grad, and its
+        # bias correction follows its own count (a parameter first reached at step 2 is corrected as at step 1)
+        self.steps = [0] * n
         self._numel = (C.c_int64 * n)(*[p.numel() for p in self.params])
         self._m = (C.c_void_p * n)(*[t.data_ptr() for t in self.exp_avg])
         self._v = (C.c_void_p * n)(*[t.data_ptr() for t in self.exp_avg_sq])
@@ -84,6 +87,8 @@ class FusedAdam:
             if g is not None and (not g.is_contiguous() or g.dtype != torch.float32):
                 g = g.contiguous().float()
             grads.append(g)
+            if g is not None:
+                self.steps[len(grads) - 1] += 1
         gp = (C.c_void_p * n)(*[(g.data_ptr() if g is not None else None) for g in grads])
         dev = self.params[0].device
         # parameter pointers are read at every step: a model moved with .to() / .cuda() after the optimizer was built
@@ -93,10 +98,11 @@ class FusedAdam:
             if self.exp_avg[i].device != p.device:
                 self.exp_avg[i], self.exp_avg_sq[i] = self.exp_avg[i].to(p.device), self.exp_avg_sq[i].to(p.device)
                 self._m[i], self._v[i] = self.exp_avg[i].data_ptr(), self.exp_avg_sq[i].data_ptr()
-        K.check(K.lib().fastegnn_adam_step(pp, gp, self._m, self._v, self._numel, n, self.step_count,
-                                           float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                           float(self.eps), float(self.weight_decay), _stream(dev)),
-                "fastegnn_adam_step")
+        steps = (C.c_int32 * n)(*self.steps)
+        K.check(K.lib().fastegnn_adam_step_v2(pp, gp, self._m, self._v, self._numel, n, steps,
+                                              float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                                              float(self.eps), float(self.weight_decay), _stream(dev)),
+                "fastegnn_adam_step_v2")
 
 
 def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, weight):

@@ -244,10 +244,11 @@ const char *fastegnn_last_error(void);
 /* ABI revision: FASTEGNN_ABI_VERSION of the header the library was built from.  It changes whenever the layout of
  * fastegnn_layer_t / fastegnn_graph_t or the meaning of an argument changes (round 3 inserted act_param: 100 -> 101; round 4 appended wgrad_batch and added fastegnn_pack_weights_all / FASTEGNN_F_WPACK_READY: 103; the fastegnn_wide_* entry points: 104;
  * round 5: fastegnn_f16_operands / fastegnn_check_finite: 105; the fused activation arguments of fastegnn_wide_linear / _dx / _dw: 106;
- * round 6: fastegnn_host_words_alloc / _free, fastegnn_zero_if_flagged, fastegnn_check_finite writes 1 instead of OR-ing: 107).
+ * round 6: fastegnn_host_words_alloc / _free, fastegnn_zero_if_flagged, fastegnn_check_finite writes 1 instead of OR-ing: 107;
+ * fastegnn_adam_step_v2 with a step count per tensor: 108).
  * A binding MUST compare it with the FASTEGNN_ABI_VERSION it was written against AND check fastegnn_sizeof_layer() /
  * fastegnn_sizeof_graph() against its own mirror of the descriptors before the first call (fastegnn_amd/_lib.py does). */
-#define FASTEGNN_ABI_VERSION 107
+#define FASTEGNN_ABI_VERSION 108
 int fastegnn_version(void);
 /* floats of the packed weight-image buffer for C virtual channels */
 size_t fastegnn_wpack_floats(int32_t C);
@@ -395,7 +396,15 @@ int fastegnn_loss_mse_mmd(const float *loc_pred, const float *loc_t, const float
                           float *g_loc, float *g_vloc, void *stream);
 /* torch.optim.Adam step (no amsgrad, L2 weight decay; main_nbody.py:137) over n_tensors tensors given as HOST arrays
  * of device pointers; a tensor whose grads[i] is null is skipped entirely, as torch.optim.Adam skips parameters whose
- * .grad is None (no weight decay, no moment update); step counts from 1. */
+ * .grad is None (no weight decay, no moment update).  steps (HOST, n_tensors): each tensor's own step count including
+ * this step, from 1 -- torch.optim.Adam's state['step'], which advances only on steps where the parameter has a .grad
+ * and sets the tensor's bias correction; not read for a tensor whose grads[i] is null.  The hyper-parameters are double,
+ * as torch.optim.Adam holds them: 1 - beta and the bias corrections are formed before any rounding to fp32.
+ * ABI revision 108. */
+int fastegnn_adam_step_v2(float *const *params, const float *const *grads, float *const *exp_avg,
+                          float *const *exp_avg_sq, const int64_t *numel, int32_t n_tensors, const int32_t *steps,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
+/* the same with one step count for every tensor (the form of revisions up to 107) */
 int fastegnn_adam_step(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                        const int64_t *numel, int32_t n_tensors, int32_t step, float lr, float beta1, float beta2,
                        float eps, float weight_decay, void *stream);

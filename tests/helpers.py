@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests (golden loading, error metrics)."""
 import glob
+import math
 import os
 
 import numpy as np
@@ -250,3 +251,66 @@ def pad_reference(name, p, h, C_, rf):
     w = torch.cat(pieces, dim=1) if len(pieces) > 1 else pieces[0]
     w = torch.nn.functional.pad(w, (0, 0, 0, rows_dst - rows))
     return w.reshape(out_shape)
+
+
+# --------------------------------------------------------------------------
+# fp64 mirror of the training-step loss (tests/test_gpu_train_kernels.py)
+# --------------------------------------------------------------------------
+U32 = 2.0 ** -24      # unit roundoff of fp32
+
+
+def mse_mmd_fp64(loc_pred, vloc, loc_t, sample_nodes, sigma, weight):
+    """oracle.fastegnn_ref.loss_mse_mmd_nodes in float64 with its gradient written out (torch.cdist's zero subgradient at
+    coincident points, which cdist's matmul form at > 25 points does not reproduce in autograd; an empty sample contributes
+    l_rv = 0) and, for every output element, the sensitivity of an fp32 evaluation of the same sums:
+    sum_i |t_i| (4 + a_i) + sqrt(n) sum_i |t_i| over its n terms t_i, a_i = |exponent| of the kernel value in the term
+    (an fp32 exp is relative-accurate to ~a u; a term below 2^-100 may be lost whole).  -> dict of loss, mse, g_loc [N,3], g_vloc [B,3,C] and s_* alongside."""
+    dt = torch.float64
+    x, tgt = loc_pred.detach().to(dt).cpu(), loc_t.detach().to(dt).cpu()
+    V = vloc.detach().to(dt).cpu().permute(0, 2, 1)                  # [B,C,3]
+    samp = sample_nodes.detach().cpu().long()
+    B, C = V.shape[0], V.shape[1]
+    S, N = samp.size(1), x.size(0)
+    i2s = 1.0 / (2.0 * sigma * sigma)
+    d = x - tgt
+    mse = (d * d).sum() / (3 * N)
+    g_loc = 2.0 * d / (3 * N)
+    s_loc = 4.0 * g_loc.abs()
+    s_loss = mse * (4.0 + math.sqrt(3 * N))
+    loss = mse.clone()
+    g_vloc = torch.zeros(B, C, 3, dtype=dt)
+    a_vloc, n_vloc = torch.zeros(B, C, 3, dtype=dt), torch.zeros(B, C, 3, dtype=dt)
+    sv_vloc = torch.zeros(B, C, 3, dtype=dt)
+
+    def pairs(X, w):
+        """terms of w * sum_{a,c} k(X_a, V_c): value, gradient on X [B,P,3] and on V"""
+        diff = X[:, :, None, :] - V[:, None, :, :]                   # [B,P,C,3]
+        dist = diff.pow(2).sum(-1).sqrt()
+        arg = dist * i2s
+        k = torch.exp(-arg)
+        f = torch.where(dist > 0, -w * k * i2s / torch.where(dist > 0, dist, torch.ones_like(dist)), torch.zeros_like(dist))
+        t = f[..., None] * diff
+        # a term near fp32's denormal range (2^-126) may come out as 0 or a flushed partial sum: it may be lost whole
+        lost = lambda a: a + (a < 2.0 ** -100).to(dt) * a / U32                      # noqa: E731
+        ta, tw = t.abs(), lost(t.abs() * (4.0 + arg[..., None]))
+        return ((w * k).sum(), lost((w * k).abs().mul(4.0 + arg)).sum(), (w * k).abs().sum(), k.numel(),
+                t.sum(2), ta.sum(2), tw.sum(2), -t.sum(1), ta.sum(1), tw.sum(1))
+
+    terms = [(V, weight / (B * C * C), None)]
+    if S:
+        terms.append((x[samp.reshape(-1)].reshape(B, S, 3), -2.0 * weight / (B * S * C), samp))
+    for X, w, idx in terms:
+        val, sw_val, sa_val, n_val, gX, aX, swX, gV, aV, swV = pairs(X, w)
+        loss = loss + val
+        s_loss = s_loss + sw_val + math.sqrt(n_val) * sa_val
+        g_vloc += gV; a_vloc += aV; sv_vloc += swV; n_vloc += X.size(1)
+        if idx is None:                                               # l_vv: both ends are virtual nodes
+            g_vloc += gX; a_vloc += aX; sv_vloc += swX; n_vloc += C
+        else:
+            n_s = 1.0 + torch.zeros(N, 3, dtype=dt).index_add_(0, idx.reshape(-1), torch.full((B * S, 3), float(C), dtype=dt))
+            a_loc = torch.zeros(N, 3, dtype=dt).index_add_(0, idx.reshape(-1), aX.reshape(-1, 3))
+            g_loc = g_loc.index_add(0, idx.reshape(-1), gX.reshape(-1, 3))
+            s_loc = s_loc + torch.zeros(N, 3, dtype=dt).index_add_(0, idx.reshape(-1), swX.reshape(-1, 3)) + n_s.sqrt() * a_loc
+    s_vloc = sv_vloc + n_vloc.clamp(min=1).sqrt() * a_vloc
+    return dict(loss=loss, mse=mse, g_loc=g_loc, g_vloc=g_vloc.permute(0, 2, 1).contiguous(),
+                s_loss=s_loss, s_mse=mse * (4.0 + math.sqrt(3 * N)), s_loc=s_loc, s_vloc=s_vloc.permute(0, 2, 1).contiguous())

@@ -77,7 +77,7 @@ def test_struct_mirrors_and_sizes():
     import ctypes as C
     assert L.fastegnn_sizeof_layer() == C.sizeof(K.LayerT)
     assert L.fastegnn_sizeof_graph() == C.sizeof(K.GraphT)
-    assert L.fastegnn_version() >= 100
+    assert L.fastegnn_version() == K.ABI_VERSION == 108
     # fp32 + split images of the 34 + 2C matrices, row-major split images (64 rows x 144 B x 3 parts) of V2, WXV0, WXX0, W3c[c]
     # 34 fixed + 2 C images (fp32 + split) and 12 fixed (7 bf16-part + 5 f16x2 forms) + C row-major images
     assert L.fastegnn_wpack_floats(16) == (34 + 32) * (4096 + 4096 + 2048) + (12 + 16) * (3 * 64 * 144 // 4)

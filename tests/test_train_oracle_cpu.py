@@ -49,3 +49,23 @@ def test_oracle_training_steps_match_reference(name):
             bad = sum(int(((p[k] - ref[k]).abs() > 2e-5).sum()) for k in p)
             tot = sum(v.numel() for v in p.values())
             assert bad <= 1e-4 * tot, (step, bad, tot)     # sign flips of gradients that are pure rounding noise
+
+
+@pytest.mark.parametrize("sizes,C,S", [([7, 7, 7], 4, 5), ([60, 50], 40, 30), ([30, 30], 1, 3)])
+def test_fp64_loss_mirror_matches_oracle_autograd(sizes, C, S):
+    """tests/helpers.py mse_mmd_fp64 (the fp64 truth of tests/test_gpu_train_kernels.py, gradient written out) against autograd
+    through oracle.loss_mse_mmd_nodes in float64, on points without coincidences (C = 40: cdist's matmul form, ~1e-9 in fp64)"""
+    from tests.helpers import mse_mmd_fp64
+    g = torch.Generator().manual_seed(C)
+    dt = torch.float64
+    N, B = sum(sizes), len(sizes)
+    loc, tgt, vloc = torch.randn(N, 3, generator=g, dtype=dt), torch.randn(N, 3, generator=g, dtype=dt), torch.randn(B, 3, C, generator=g, dtype=dt)
+    off = np.cumsum([0] + sizes)
+    samp = torch.stack([int(off[b]) + torch.randint(0, sizes[b], (S,), generator=g) for b in range(B)])
+    a, v = loc.clone().requires_grad_(True), vloc.clone().requires_grad_(True)
+    loss, mse = R.loss_mse_mmd_nodes(a, v, tgt, samp, 1.3, 0.7)
+    loss.backward()
+    t = mse_mmd_fp64(loc, vloc, tgt, samp, 1.3, 0.7)
+    assert abs(loss.item() - t["loss"].item()) < 1e-10 and abs(mse.item() - t["mse"].item()) < 1e-14
+    assert rel_err(t["g_loc"], a.grad) < 1e-8 and rel_err(t["g_vloc"], v.grad) < 1e-8
+    assert (t["s_loc"] >= 4 * t["g_loc"].abs()).all() and (t["s_vloc"] >= t["g_vloc"].abs()).all()
