@@ -87,7 +87,30 @@ __global__ __launch_bounds__(256) void graph_post_bwd_kernel(GraphPostBwdArgs a)
   }
 }
 
+// g_HvT_out == NULL && g_h_out == NULL: no gradient arrives for Hv (and the forward of this layer skipped node_model_virtual) -- the
+// coordinate part alone (the same expressions as above); g_HvT starts from zero (graph_pre_bwd adds the g_Bc part), g_poolV is zero and
+// not written: the virtual stage does not read it then
+__global__ __launch_bounds__(256) void graph_post_bwd_coords_kernel(const float *xsum, const float *g_Z_out, float *g_Z, float *g_poolX,
+                                                                    float *g_HvT, int B, int C) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 3 * C; i += gridDim.x * blockDim.x) {
+    const int b = i / (3 * C);
+    const float g = g_Z_out[i];
+    g_Z[i] = g;
+    g_poolX[i] = g / fmaxf(xsum[b * 4 + 3], 1.f);
+  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * C * H; i += gridDim.x * blockDim.x) g_HvT[i] = 0.f;
+}
+
 int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared) {
+  if (!L->g_HvT_out && !has(L, FASTEGNN_F_RF)) {
+    FE_REQUIRE(!L->g_h_out, "graph_post_backward: g_HvT_out is null and g_h_out is not (both null: no gradient for h / Hv; otherwise neither)");
+    FE_REQUIRE(L->xsum && L->g_Z_out && L->g_Z && L->g_HvT && L->g_poolX, "graph_post_backward: null buffer");
+    int grid = cdiv((long)L->B * L->C * H, 256);
+    if (grid > 256) grid = 256;
+    if (grid < 1) grid = 1;
+    { ProfScope _ps_graph_post_bwd_kernel(K_GRAPH_POST_BWD, st); hipLaunchKernelGGL(graph_post_bwd_coords_kernel, dim3(grid), dim3(256), 0, st, L->xsum, L->g_Z_out, L->g_Z, L->g_poolX, L->g_HvT, L->B, L->C); }
+    return check_launch("graph_post_bwd_coords_kernel");   // no node_mlp_virtual jobs: their gradients are not defined
+  }
   FE_REQUIRE(L->xsum && L->HvT && L->poolV && L->g_Z_out && L->g_HvT_out && L->g_Z && L->g_HvT && L->g_poolV &&
                  L->g_poolX && L->wg_node && L->grads && L->wpack,
              "graph_post_backward: null buffer");

@@ -404,14 +404,18 @@ namespace fe {
 
 int virt_forward(const fastegnn_layer_t *L, hipStream_t st) {
   const bool egnn = has(L, FASTEGNN_F_EGNN);
-  FE_REQUIRE(L->h && L->A && L->x && L->vel && L->aggm && L->aggx && L->svel && L->npre && L->h_out && L->x_out &&
+  // h_out == NULL && HvT_out == NULL (FastEGNN wiring): the node update of this layer is not wanted -- npre and poolV are not written
+  // and may be null as well (include/fastegnn_hip.h)
+  const bool node = egnn || has(L, FASTEGNN_F_RF) || L->h_out;
+  FE_REQUIRE(node || !L->HvT_out, "virt_forward: h_out is null and HvT_out is not (both null: no node update; otherwise neither)");
+  FE_REQUIRE(L->h && L->A && L->x && L->vel && L->aggm && L->aggx && L->svel && (!node || (L->npre && L->h_out)) && L->x_out &&
                  L->batch && L->wpack,
              "virt_forward: null buffer");
-  FE_REQUIRE(egnn ? L->C == 0 : (L->Bc && L->Z && L->poolV && L->poolX && L->C >= 1 && L->C <= 64),
+  FE_REQUIRE(egnn ? L->C == 0 : (L->Bc && L->Z && (!node || L->poolV) && L->poolX && L->C >= 1 && L->C <= 64),
              "virt_forward: virtual_channels must be in [1,64] (0 with FASTEGNN_F_EGNN) and the virtual buffers non-null");
   FE_REQUIRE(L->na == 0 || L->node_attr, "virt_forward: node_attr null");
   if (L->C > 0) {
-    (void)hipMemsetAsync(L->poolV, 0, (size_t)L->B * L->C * H * sizeof(float), st);
+    if (node) (void)hipMemsetAsync(L->poolV, 0, (size_t)L->B * L->C * H * sizeof(float), st);
     (void)hipMemsetAsync(L->poolX, 0, (size_t)L->B * 3 * L->C * sizeof(float), st);
   }
   if (L->N == 0) return check_launch("virt_forward(memset)");
@@ -425,7 +429,12 @@ int virt_forward(const fastegnn_layer_t *L, hipStream_t st) {
   {
     ProfScope _ps_virt_fwd_kernel(K_VIRT_FWD, st);
     const size_t lds = virt_fwd_lds_bytes(L->C, pair);
-    if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL(virt_fwd_kernel<GM_BF16>, dim3(grid), dim3(64 * VIRT_WAVES), lds, st, a);
+    if (!node) {
+      if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL((virt_fwd_kernel<GM_BF16, false, false>), dim3(grid), dim3(64 * VIRT_WAVES), lds, st, a);
+      else if (pair) launch_virt_fwd_pair_nonode(a, grid, lds, st);
+      else hipLaunchKernelGGL((virt_fwd_kernel<GM_VIRT_FWD, false, false>), dim3(grid), dim3(64 * VIRT_WAVES), lds, st, a);
+    }
+    else if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL(virt_fwd_kernel<GM_BF16>, dim3(grid), dim3(64 * VIRT_WAVES), lds, st, a);
     else if (pair) launch_virt_fwd_pair(a, grid, lds, st);   // (virt_fwd_pair.hip: its own translation unit, see virt_fwd.h)
     else hipLaunchKernelGGL(virt_fwd_kernel<GM_VIRT_FWD>, dim3(grid), dim3(64 * VIRT_WAVES), lds, st, a);
   }
@@ -475,7 +484,24 @@ __global__ __launch_bounds__(256) void graph_post_fwd_kernel(GraphPostArgs a) {
     if (valid) vstore_row(a.HvT_out + (size_t)m * H, q, out);
   }
 }
+// HvT_out == NULL && h_out == NULL: node_model_virtual is not wanted -- the coordinate part alone (the same expression as above)
+__global__ __launch_bounds__(256) void graph_post_fwd_coords_kernel(const float *xsum, const float *Z, const float *poolX, float *Z_out,
+                                                                    int B, int C) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 3 * C; i += gridDim.x * blockDim.x) {
+    const int b = i / (3 * C);
+    Z_out[i] = Z[i] + poolX[i] / fmaxf(xsum[b * 4 + 3], 1.f);
+  }
+}
 int graph_post_forward(const fastegnn_layer_t *L, hipStream_t st) {
+  if (!L->HvT_out && !has(L, FASTEGNN_F_RF)) {
+    FE_REQUIRE(!L->h_out, "graph_post_forward: HvT_out is null and h_out is not (both null: no node update; otherwise neither)");
+    FE_REQUIRE(L->xsum && L->Z && L->poolX && L->Z_out, "graph_post_forward: null buffer");
+    int grid = cdiv((long)L->B * 3 * L->C, 256);
+    if (grid > 256) grid = 256;
+    if (grid < 1) grid = 1;
+    { ProfScope _ps_graph_post_fwd_kernel(K_GRAPH_POST_FWD, st); hipLaunchKernelGGL(graph_post_fwd_coords_kernel, dim3(grid), dim3(256), 0, st, L->xsum, L->Z, L->poolX, L->Z_out, L->B, L->C); }
+    return check_launch("graph_post_fwd_coords_kernel");
+  }
   FE_REQUIRE(L->xsum && L->Z && L->HvT && L->poolV && L->poolX && L->Z_out && L->HvT_out && L->wpack,
              "graph_post_forward: null buffer");
   GraphPostArgs a{L->xsum, L->Z, L->HvT, L->poolV, L->poolX, L->wpack, L->params[FASTEGNN_P_NODEV0_B],

@@ -117,6 +117,33 @@ __global__ __launch_bounds__(64 * VB_NODE_WAVES) void virt_bwd_node_kernel(VirtN
   }
 }
 
+// B4a when no gradient arrives for h (g_h_out == NULL && g_HvT_out == NULL: the forward skipped this layer's node update): g_np = 0, so
+// g_h (the part of this stage) and g_aggm are zero rows; the per-node scalars of the coordinate update are the expressions above.
+// One thread per 16-byte piece of a row.
+__global__ __launch_bounds__(256) void virt_bwd_node_skip_kernel(const float *g_x_out, const float *vel, float *g_h, float *g_aggm,
+                                                                 float *g_aggx, float *g_svel, float *g_sgrav, int N, int flags,
+                                                                 float g0, float g1, float g2) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * (H / 4)) return;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  reinterpret_cast<f32x4 *>(g_h)[i] = z;
+  reinterpret_cast<f32x4 *>(g_aggm)[i] = z;
+  if ((i & (H / 4 - 1)) == 0) {
+    const size_t n = i / (H / 4);
+    const float g[3] = {g0, g1, g2};
+    float sv = 0.f, sg = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float gxn = g_x_out[n * 3 + k];
+      g_aggx[n * 3 + k] = gxn;
+      sv += gxn * vel[n * 3 + k];
+      sg += gxn * g[k];
+    }
+    g_svel[n] = sv;
+    if (flags & FASTEGNN_F_GRAVITY) g_sgrav[n] = sg;
+  }
+}
+
 // =====================================================================================
 // B4b  Gv[c][n][:] = g_poolV[batch[n], c][:] + W3c[c]^T g_np[n][:]
 // (d loss / d v[n,c,:] through node_mlp.0's flat(v) block (:157-158) and node_model_virtual's pool (:170))
@@ -979,7 +1006,11 @@ __device__ int g_vbs_dog[64];
 #endif
 constexpr int VBS_SPIN_LIMIT = 1 << 23;
 __device__ int g_vbs_timeouts = 0;
-template <bool ATT>
+// NODE = false: no gradient arrives for h / Hv (g_h_out == NULL && g_HvT_out == NULL in the layer descriptor): g_np = 0 and g_poolV = 0, so
+// Gv = 0 -- no g_np row, no W3c^T stage and product, no (g_np, v) contraction: ring A carries (g_ux, g_uX, v) to wave 3 alone, and wave 6
+// is a sixth producer (measured against sitting the launch out: DESIGN.md section 11).  The ticket / flag protocol is NODE = true's:
+// READY still marks "the parity's pool rows are clear".  NODE = true is the kernel as it was.
+template <bool ATT, bool NODE = true>
 __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A) {
   constexpr int SM = GM_F16;
   typedef typename OperandOf<SM>::type SOp;
@@ -1032,15 +1063,17 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
   const int nblk = max(1, (nt + A.block / 2) / A.block);
   const int BT = (nt + nblk - 1) / nblk;
   const int nphase = nblk * C;
-  if (wv == 0) stage_w3(0);
-  if (wv == 1 && nphase > 1) stage_w3(1);
+  if constexpr (NODE) {
+    if (wv == 0) stage_w3(0);
+    if (wv == 1 && nphase > 1) stage_w3(1);
+  }
   __syncthreads();
   if (threadIdx.x < 2 && (int)threadIdx.x < nphase) ctrl[VBSC_READY + threadIdx.x] = threadIdx.x + 1;   // READY[ph % NPH] == ph + 1: phase ph may run
   __syncthreads();
   // -DFE_VBS_5P=1 (default): wave 6 is a third consumer that takes the dW3c contraction off wave 7 -- with six producers wave 7's two
   // contractions from two rings paced the kernel (virt_bwd 4.41 ms per step; 3.47 with the dW3c products skipped: gpurun_out/cs3)
   constexpr bool FIVEP = FE_VBS_5P != 0;
-  const bool consumer = wv == VB_CONS_X || wv == VB_CONS_XX || (FIVEP && wv == VB_CONS_V2);
+  const bool consumer = wv == VB_CONS_X || wv == VB_CONS_XX || (FIVEP && NODE && wv == VB_CONS_V2);
   const int total = nt * C;                       // units = tickets per ring
   const int cur = a.batch[t_lo * 16];             // graph whose pools this workgroup accumulates in LDS
   const bool tanh_on = a.flags & FASTEGNN_F_TANH;
@@ -1148,10 +1181,11 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
       int since_w = 0;
       int *drainedA = ctrl + VBSC_DRAINED + VB_MAXRING, *drainedB = ctrl + VBSC_DRAINED + 2 * VB_MAXRING;
 #ifdef FE_VBS_SWAP   // measured alternative: the light (g_vp, t) contraction beside producer 2 on SIMD 2, (g_np, v) beside wave 3 on SIMD 3
-      const bool doV2 = FIVEP ? wv == VB_CONS_V2 : wv == VB_CONS_XX, doW = wv == VB_CONS_XX;
+      const bool doV2n = FIVEP ? wv == VB_CONS_V2 : wv == VB_CONS_XX, doWn = wv == VB_CONS_XX;
 #else
-      const bool doV2 = wv == VB_CONS_XX, doW = FIVEP ? wv == VB_CONS_V2 : wv == VB_CONS_XX;
+      const bool doV2n = wv == VB_CONS_XX, doWn = FIVEP ? wv == VB_CONS_V2 : wv == VB_CONS_XX;
 #endif
+      const bool doV2 = NODE ? doV2n : true, doW = NODE && doWn;   // (NODE = false: wave 7 is the only wave here, and ring B its only ring)
       // acc (+ the parity's scratch tile) -> the channel's running sum over the blocks, ACCUMULATOR order, plain read-modify-write
       // (the slab is this wave's own; the reduction kernel reads that order: WgJob::acc32)
       auto flush_w = [&](WgAcc32 &acc, float ig, float it, int slot, bool have, float *dst, bool add) {
@@ -1409,28 +1443,34 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
       }
       VB2_T(6)   // head X: the same
       // Gv = g_poolV[b, c] + W3c[c]^T g_np is formed in registers; the g_np row also rides to wave 7 in the ring slot
-      const Vec gnp = vb_mask(vload_u(A.g_np, offN), valid);
+      Vec gnp = vzero();
+      if constexpr (NODE) gnp = vb_mask(vload_u(A.g_np, offN), valid);
       {   // (g_ux, v), (g_uX, v), (g_np, v) to waves 3 and 7: one slot of ring A, free once both have drained it
         int tk = 0;
         if (l == 0) tk = atomicAdd(&ctrl[VBSC_HEAD + 0], 1);
         tk = __builtin_amdgcn_readfirstlane(tk);
         const int sl = tk % A.ringA, round = tk / A.ringA;
         VBS_SPIN(4, vb_ld(&ctrl[VBSC_DRAINED + 0 * VB_MAXRING + sl]) != round, 2);
-        VBS_SPIN(5, vb_ld(&ctrl[VBSC_DRAINED + 1 * VB_MAXRING + sl]) != round, 2);
+        if constexpr (NODE) VBS_SPIN(5, vb_ld(&ctrl[VBSC_DRAINED + 1 * VB_MAXRING + sl]) != round, 2);   // (NODE = false: one reader)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
         float *slot = ringA + sl * VBS_SLOT_A;
         vb_tile_store(slot, j, q, g_ux);
         vb_tile_store(slot + VB_TILE, j, q, g_uX);
         vb_tile_store(slot + 2 * VB_TILE, j, q, valid ? v : vzero());
-        vb_tile_store(slot + 3 * VB_TILE, j, q, gnp);
-        if (l == 0) ctrl[VBSC_SLOTCH + sl] = c | (nb << 8) | (blk << 20);
+        if constexpr (NODE) {
+          vb_tile_store(slot + 3 * VB_TILE, j, q, gnp);
+          if (l == 0) ctrl[VBSC_SLOTCH + sl] = c | (nb << 8) | (blk << 20);
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
         if (l == 0) vb_st(&ctrl[VBSC_FILLED + sl], round + 1);
         asm volatile("" ::: "memory");
       }
       VB2_T(7)   // g_np row, publish (g_ux, g_uX, v, g_np) to ring A (incl. the wait for a drained slot)
-      Vec g_v = vb_mask(vload_u(A.g_poolV, offB), valid);
-      gemm64_f2_scaled(w3 + (ph & 1) * VBS_W3_WORDS, vsplit2_scaled(gnp), g_v);
+      Vec g_v = vzero();
+      if constexpr (NODE) {
+        g_v = vb_mask(vload_u(A.g_poolV, offB), valid);
+        gemm64_f2_scaled(w3 + (ph & 1) * VBS_W3_WORDS, vsplit2_scaled(gnp), g_v);
+      }
       mmT(1, g_ux, g_v);
       mmT(2, g_uX, g_v);
       VB2_T(8)   // three scaled gradient splits + W3c^T g_np and the two transposed head products
@@ -1527,7 +1567,7 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
         }
         if (l == 0) ctrl[VBSC_DONE + ph % VBS_NPH] = 0;   // (the flag slot is reused VBS_NPH phases later)
         if (ph + 2 < nphase) {
-          stage_w3(ph + 2);
+          if constexpr (NODE) stage_w3(ph + 2);
           // (a RELEASE store at workgroup scope between compiler barriers: as a relaxed store behind a fence the compiler sank it out
           // of the unit loop -- legal for a relaxed atomic, fatal here: this very wave goes on to spin on the flag of a later channel
           // while the others wait for this one.  Found with the spin watchdog of -DFE_VBS_WATCHDOG, tools/gpu_vbs_dog.py)
@@ -1599,12 +1639,12 @@ size_t virt_pc_wg_floats(size_t N, size_t C) {
 }
 
 // B4c': the (node, channel) part in the channel-phased form -- one kernel, then the fixed-order reduction of its partial slabs
-static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp) {
+static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp, bool node) {
   const int C = L->C;
   const bool att = has(L, FASTEGNN_F_ATTENTION);
   float *const *g = L->grads;
   const int grid = virt_cs_grid(L->N);
-  FE_REQUIRE(L->g_poolV, "virt_backward: g_poolV null");
+  FE_REQUIRE(!node || L->g_poolV, "virt_backward: g_poolV null");
   WgradBatch bb(L->wg_slab, st, false, WG_SLABS / 2, WG_SLABS / 2);
   VirtCsArgs A;
   A.f = make_virt_args(L);
@@ -1636,10 +1676,15 @@ static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, 
   {
     ProfScope ps(K_VIRT_BWD, st);
     const dim3 g3(grid), b3(64 * VB_WAVES);
-    if (att) hipLaunchKernelGGL((virt_bwd_cs_kernel<true>), g3, b3, lds, st, A);
+    if (!node) {
+      if (att) hipLaunchKernelGGL((virt_bwd_cs_kernel<true, false>), g3, b3, lds, st, A);
+      else hipLaunchKernelGGL((virt_bwd_cs_kernel<false, false>), g3, b3, lds, st, A);
+    }
+    else if (att) hipLaunchKernelGGL((virt_bwd_cs_kernel<true>), g3, b3, lds, st, A);
     else hipLaunchKernelGGL((virt_bwd_cs_kernel<false>), g3, b3, lds, st, A);
   }
   if ((rc = check_launch("virt_bwd_cs_kernel"))) return rc;
+  if (!node) return bb.finish();   // no (g_np, v) slabs: node_mlp.0 has no gradient
   // node_mlp.0 block of channel c (column 2H + k C + c, k = feature of v): one slab set per channel, written by wave 7
   const int ld_n0 = 2 * H + H * C + L->na;
   if ((rc = bb.add_slabs_ext(A.w_slab, g[FASTEGNN_P_NODE0_W], ld_n0, 2 * H, C, grid, C, 1))) return rc;
@@ -1647,8 +1692,10 @@ static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, 
 }
 
 // B4b + B4c: the (node, channel) part -- Gv, then the producer / consumer kernel and its weight gradients
-static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp) {
-  if (virt_cs_applies(L->N, L->C, L->flags)) return virt_backward_channels_cs(L, st, wg_gnp);
+// node = false (no gradient arrives for h / Hv): the phased form runs its NODE = false instantiation; the tile-major form (small inputs,
+// bf16 operands) takes Gv = 0 like the FastRF wiring does and queues no node_mlp.0 job
+static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp, bool node) {
+  if (virt_cs_applies(L->N, L->C, L->flags)) return virt_backward_channels_cs(L, st, wg_gnp, node);
   const int N = L->N, C = L->C, ntiles = cdiv(N, 16);
   const bool bf = has(L, FASTEGNN_F_BF16), att = has(L, FASTEGNN_F_ATTENTION), rf = has(L, FASTEGNN_F_RF);
   float *const *g = L->grads;
@@ -1658,6 +1705,9 @@ static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, flo
   float *gA_part = Gv + cstride * C, *gx_part = gA_part + (size_t)256 * VB_FINE_TILES * (NGF - 1) * 16 * H;
   int rc;
   if (rf) {   // FastRF: no node_model and no pooled messages -- d/dv is the recomputed heads' part alone
+    (void)hipMemsetAsync(Gv, 0, cstride * C * sizeof(float), st);
+  } else if (!node) {   // g_np = 0 and g_poolV = 0: B4b is a fill (timed as the stage it stands in for)
+    ProfScope ps(K_VIRT_BWD_GV, st);
     (void)hipMemsetAsync(Gv, 0, cstride * C * sizeof(float), st);
   } else {
     const int ngroups = cdiv(C, VB_GV_CH);
@@ -1715,7 +1765,7 @@ static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, flo
     if ((rc = check_launch("virt_bwd_combine_kernel"))) return rc;
   }
   // node_mlp.0 block of channel c: (g_np, v[:, c]) -- one batch slice per channel
-  if (!rf) {
+  if (!rf && node) {
     const int ld_n0 = 2 * H + H * C + L->na;
     if ((rc = bb.add(wg_gnp, H, wg_v, H, N, g[FASTEGNN_P_NODE0_W], ld_n0, 2 * H, C, nullptr, C, 0, (long)cstride, 1))) return rc;
   }
@@ -1726,13 +1776,17 @@ static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, flo
 // node_mlp jobs); the EGNN baseline (FASTEGNN_F_EGNN, C = 0: B4a and the node_mlp jobs only).
 int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared) {
   const bool egnn = has(L, FASTEGNN_F_EGNN), rf = has(L, FASTEGNN_F_RF);
-  FE_REQUIRE(L->h && L->A && L->x && L->vel && L->aggm && L->npre && L->batch && L->wpack && (!egnn || L->aggx),
+  // g_h_out == NULL && g_HvT_out == NULL (FastEGNN wiring): no gradient arrives for h / Hv, and the forward of this layer skipped the
+  // node update -- npre and g_poolV are not read and may be null as well (include/fastegnn_hip.h)
+  const bool node = egnn || rf || L->g_h_out;
+  FE_REQUIRE(node || !L->g_HvT_out, "virt_backward: g_h_out is null and g_HvT_out is not (both null: no gradient for h / Hv; otherwise neither)");
+  FE_REQUIRE(L->h && L->A && L->x && L->vel && L->aggm && (!node || L->npre) && L->batch && L->wpack && (!egnn || L->aggx),
              "virt_backward: null saved buffer");
-  FE_REQUIRE(L->g_h_out && L->g_x_out && L->g_h && L->g_x && L->g_A && L->g_aggm && L->g_aggx && L->g_svel && L->wg_node &&
+  FE_REQUIRE((!node || L->g_h_out) && L->g_x_out && L->g_h && L->g_x && L->g_A && L->g_aggm && L->g_aggx && L->g_svel && L->wg_node &&
                  L->grads && L->wg_slab,
              "virt_backward: null gradient buffer");
   FE_REQUIRE(egnn ? L->C == 0
-                  : (L->Bc && L->Z && (rf || L->g_poolV) && L->g_poolX && L->g_Bc && L->g_Zp && L->wg_virt && L->C >= 1 && L->C <= 64),
+                  : (L->Bc && L->Z && (rf || !node || L->g_poolV) && L->g_poolX && L->g_Bc && L->g_Zp && L->wg_virt && L->C >= 1 && L->C <= 64),
              "virt_backward: virtual buffers null or virtual_channels outside [1,64] (0 with FASTEGNN_F_EGNN)");
   const int N = L->N, C = L->C;
   if (C > 0) {
@@ -1747,7 +1801,11 @@ int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared)
   float *wg_t3 = L->wg_node, *wg_gnp = L->wg_node + (size_t)N * H;
   const int ntiles = cdiv(N, 16);
   int rc;
-  {   // B4a
+  if (!node) {   // B4a without the node_mlp adjoint
+    ProfScope ps(K_VIRT_BWD_NODE, st);
+    hipLaunchKernelGGL(virt_bwd_node_skip_kernel, dim3(cdiv((long)N * (H / 4), 256)), dim3(256), 0, st, L->g_x_out, L->vel, L->g_h, L->g_aggm,
+                       L->g_aggx, L->g_svel, L->g_sgrav, N, L->flags, L->gravity[0], L->gravity[1], L->gravity[2]);
+  } else {   // B4a
     VirtNodeArgs a{L->g_h_out, L->npre, L->g_x_out, L->vel, L->aggx, L->wpack, wg_t3, wg_gnp, L->g_h, L->g_aggm, L->g_aggx,
                    L->g_svel, L->g_sgrav, N, L->flags, C, {L->gravity[0], L->gravity[1], L->gravity[2]}, L->act_param};
     int grid = cdiv(ntiles, VB_NODE_WAVES);
@@ -1761,10 +1819,10 @@ int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared)
     (void)hipMemcpyAsync(L->g_x, L->g_x_out, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
     (void)hipMemsetAsync(L->g_A, 0, (size_t)N * H * sizeof(float), st);
     if ((rc = check_launch("virt_backward(C = 0)"))) return rc;
-  } else if ((rc = virt_backward_channels(L, st, wg_gnp))) {
+  } else if ((rc = virt_backward_channels(L, st, wg_gnp, node))) {
     return rc;
   }
-  if (rf) return FASTEGNN_OK;   // no node_mlp
+  if (rf || !node) return FASTEGNN_OK;   // no node_mlp (FastRF) / no gradient for it
   WgradBatch local(L->wg_slab, st);
   WgradBatch &wb = shared ? *shared : local;
   wb.round = bf;

@@ -18,7 +18,10 @@ constexpr int VIRT_FWD_IMG_FLOATS_PAIR = 3 * IMG3 + VIRT_FWD_PAIR_STAGE;
 inline size_t virt_fwd_lds_bytes(int C, bool pair = false) {
   return (size_t)((pair ? VIRT_FWD_IMG_FLOATS_PAIR : VIRT_FWD_IMG_FLOATS) + VV_COUNT * H + 2 * (C * H + ((3 * C + 3) & ~3)) + 4) * sizeof(float);   // + 4 control words
 }
-template <int MODE, bool PAIR = false>
+// NODE = false: the node update of this layer is not wanted (h_out == NULL && HvT_out == NULL in the layer descriptor: nothing reads h / Hv
+// after the last layer of FastEGNN) -- no W3c stage, no node_mlp.0 accumulation, no node-MLP tail, no npre / h_out stores, no poolV sums;
+// x_out and poolX are what NODE = true computes.  NODE = true is the kernel as it was.
+template <int MODE, bool PAIR = false, bool NODE = true>
 __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
   static_assert(!PAIR || MODE == GM_F16, "the two-waves-per-tile walk is built for the f16x2 images");
   constexpr int TPS = PAIR ? VIRT_WAVES / 2 : VIRT_WAVES;   // tiles per step of a workgroup
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
   const int t_lo = (int)((long)blockIdx.x * ntiles / gridDim.x), t_hi = (int)((long)(blockIdx.x + 1) * ntiles / gridDim.x);
   const float invC = C > 0 ? 1.0f / (float)C : 0.f;
   const bool clamp_aggx = a.flags & FASTEGNN_F_EGNN;   // basic.py:310
-  const bool rf = a.flags & FASTEGNN_F_RF;             // FastRF.py:155-186: no node_model / node_model_virtual
+  const bool rf = !NODE || (a.flags & FASTEGNN_F_RF);  // FastRF.py:155-186: no node_model / node_model_virtual (nor with NODE = false)
   int cur = -1;  // graph the LDS pool accumulators belong to
   VF_T0()
   auto flush_pools = [&]() {
@@ -231,14 +234,18 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
       const int co = ((wv & 3) * 16 + j) * TS;
       __syncthreads();            // every wave is done with the stage
       if (grp == 1 && active) {
+        if constexpr (NODE) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4 *>(&comb[co + 16 * t + 4 * q]) = nodeacc.t[t];
+          for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4 *>(&comb[co + 16 * t + 4 * q]) = nodeacc.t[t];
+        }
         if (q == 0) *reinterpret_cast<f32x4 *>(&comb[co + H]) = f32x4{transv[0], transv[1], transv[2], 0.f};
       }
       __syncthreads();
       if (grp == 0 && active) {
+        if constexpr (NODE) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) nodeacc.t[t] += *reinterpret_cast<const f32x4 *>(&comb[co + 16 * t + 4 * q]);
+          for (int t = 0; t < 4; ++t) nodeacc.t[t] += *reinterpret_cast<const f32x4 *>(&comb[co + 16 * t + 4 * q]);
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k) transv[k] += comb[co + H + k];
       }
@@ -249,25 +256,31 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
       __syncthreads();
       for (int i = threadIdx.x; i < 16 * TS; i += blockDim.x) comb[i] = 0.f;
       __syncthreads();
+      if constexpr (NODE) {
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) atomicAdd(&comb[j * TS + 16 * t + 4 * q + r], nodeacc.t[t][r]);
+          for (int r = 0; r < 4; ++r) atomicAdd(&comb[j * TS + 16 * t + 4 * q + r], nodeacc.t[t][r]);
+      }
       if (q == 0) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) atomicAdd(&comb[j * TS + H + k], transv[k]);
       }
       __syncthreads();
       if (own) {
+        if constexpr (NODE) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) nodeacc.t[t] = *reinterpret_cast<const f32x4 *>(comb + j * TS + 16 * t + 4 * q);
+          for (int t = 0; t < 4; ++t) nodeacc.t[t] = *reinterpret_cast<const f32x4 *>(comb + j * TS + 16 * t + 4 * q);
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k) transv[k] = comb[j * TS + H + k];
       }
       __syncthreads();
     }
-    if (active && rf && own) {   // the node features pass through unchanged (FastRF.py:186)
-      if (valid) vstore_row(a.h_out + (size_t)n * H, q, vload_row(a.h + (size_t)nc * H, q));
+    if constexpr (NODE) {
+      if (active && rf && own) {   // the node features pass through unchanged (FastRF.py:186)
+        if (valid) vstore_row(a.h_out + (size_t)n * H, q, vload_row(a.h + (size_t)nc * H, q));
+      }
     }
     if (!rf) {
       // node_model: node_mlp.0 on [h | agg | flat(v) | node_attr]  (:153-166).  The three node-level images (W3A, W3B,

@@ -513,6 +513,14 @@ class _PadParams(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+def _skip_last_node_update(spec) -> bool:
+    """The last layer's node_model / node_model_virtual feed h and Hv, which FastEGNN.forward does not return (models/FastEGNN.py:266-276):
+    their forward and their adjoint (on a gradient that is identically zero) are not run -- null h_out / HvT_out and g_h_out / g_HvT_out in the
+    layer descriptor (include/fastegnn_hip.h).  FASTEGNN_KEEP_DEAD_NODE_UPDATE=1 is a DIAGNOSTIC: it runs them as every other layer's, the
+    baseline the skip is tested and measured against; read per call, so that a test can flip it."""
+    return not (spec.flags & K.F_RF) and os.environ.get("FASTEGNN_KEEP_DEAD_NODE_UPDATE", "0") in ("", "0")
+
+
 class _FastEGNNFunction(torch.autograd.Function):
     """Whole-model forward/backward on the HIP library (one C-ABI call per layer and direction)."""
 
@@ -557,16 +565,22 @@ class _FastEGNNFunction(torch.autograd.Function):
             keep.append(Lp)
             packs[i] = C.pointer(Lp)
         K.check(lib.fastegnn_pack_weights_all(packs, spec.n_layers, st), "fastegnn_pack_weights_all")
+        skip_last = _skip_last_node_update(spec)
         for i in range(spec.n_layers):
             tab = tabs[i]
+            dead = skip_last and i == spec.n_layers - 1   # this layer's node update is read by nothing: its buffers stay null
             b = dict(h=h, x=x, Z=Z, HvT=HvT, wpack=wpack_all[i])
-            b.update(_carve(dev, dict(
+            shapes = dict(
                 P=(N, H), QX=(N, K.QX_LD), A=(N, H), svel=(N,), sgrav=(N,), xsum=(B, 4),
-                Bc=(B, Cn, H), aggm=(N, H), npre=(N, H), poolV=(B, Cn, H))))
+                Bc=(B, Cn, H), aggm=(N, H), npre=(N, H), poolV=(B, Cn, H))
+            if dead:
+                del shapes["npre"], shapes["poolV"]
+            b.update(_carve(dev, shapes))
             # outputs / forward-only scratch: separate allocations so that they can be freed individually
             b.update(_carve(dev, dict(aggx=(N, 3), poolX=(B, 3, Cn))))
-            b.update(h_out=torch.empty(N, H, **f32), x_out=torch.empty(N, 3, **f32),
-                     Z_out=torch.empty(B, 3, Cn, **f32), HvT_out=torch.empty(B, Cn, H, **f32))
+            b.update(x_out=torch.empty(N, 3, **f32), Z_out=torch.empty(B, 3, Cn, **f32))
+            if not dead:
+                b.update(h_out=torch.empty(N, H, **f32), HvT_out=torch.empty(B, Cn, H, **f32))
             L = _new_layer(spec, N, B, graph)
             L.flags |= K.F_WPACK_READY
             _fill(L, batch=batch32, gptr=gptr, vel=node_vel, params=tab.addr(), **b)
@@ -577,11 +591,12 @@ class _FastEGNNFunction(torch.autograd.Function):
                 L.node_attr = node_attr.data_ptr()
             K.check(lib.fastegnn_layer_forward(C.byref(L), st), f"fastegnn_layer_forward[{i}]")
             saved.append(b)
-            h, x, Z, HvT = b["h_out"], b["x_out"], b["Z_out"], b["HvT_out"]
+            h, x, Z, HvT = b.get("h_out"), b["x_out"], b["Z_out"], b.get("HvT_out")
             # outputs of layer i are the inputs of layer i+1; drop what backward does not need
             for k in ("aggx", "poolX", "h_out", "x_out", "Z_out", "HvT_out"):
-                del b[k]
+                b.pop(k, None)
         ctx.spec, ctx.graph, ctx.saved = spec, graph, saved
+        ctx.skip_last = skip_last and spec.n_layers >= 1   # the backward of THIS forward: the switch may have changed by then
         ctx.misc = (batch32, gptr, ea_sorted, node_attr, node_feat, node_vel, params)
         return x, Z
 
@@ -608,10 +623,11 @@ class _FastEGNNFunction(torch.autograd.Function):
         for p, s in zip(params, sizes):
             grads.append(flat[off:off + p.numel()].view_as(p))
             off += s
-        g_h = torch.zeros(N, H, **f32)
+        skip_last = ctx.skip_last   # the last layer takes null g_h_out / g_HvT_out: no gradient arrives for h / Hv
+        g_h = None if skip_last else torch.zeros(N, H, **f32)
         g_x = (g_loc if g_loc is not None else torch.zeros(N, 3, **f32)).contiguous().float()
         g_Z = (g_vloc if g_vloc is not None else torch.zeros(B, 3, Cn, **f32)).contiguous().float()
-        g_HvT = torch.zeros(B, Cn, H, **f32)
+        g_HvT = None if skip_last else torch.zeros(B, Cn, H, **f32)
         g_vel = torch.zeros(N, 3, **f32)
         want_ea = ctx.needs_input_grad[4] and ea_sorted is not None and E > 0
         want_na = ctx.needs_input_grad[5] and node_attr is not None
@@ -631,8 +647,11 @@ class _FastEGNNFunction(torch.autograd.Function):
             L = _new_layer(spec, N, B, graph)
             out = dict(g_h=torch.empty(N, H, **f32), g_x=torch.empty(N, 3, **f32),
                        g_Z=torch.empty(B, 3, Cn, **f32), g_HvT=torch.empty(B, Cn, H, **f32))
+            up = dict(g_x_out=g_x, g_Z_out=g_Z)
+            if g_h is not None:
+                up.update(g_h_out=g_h, g_HvT_out=g_HvT)
             _fill(L, batch=batch32, gptr=gptr, vel=node_vel, params=ptab.addr(), grads=gtab.addr(),
-                  g_h_out=g_h, g_x_out=g_x, g_Z_out=g_Z, g_HvT_out=g_HvT, g_vel=g_vel, **b, **out, **scratch)
+                  g_vel=g_vel, **up, **b, **out, **scratch)
             L.QX_src = b["QX"].data_ptr()
             L.g_QX = scratch["g_QX_src"].data_ptr()
             if ea_sorted is not None:
@@ -657,7 +676,8 @@ class _FastEGNNFunction(torch.autograd.Function):
                                             K.ptr(grads[1]), K.ptr(grads[2]), K.ptr(g_nf), st),
                 "fastegnn_embed_backward")
         # The last layer's node_mlp / node_mlp_virtual only feed h and Hv, which nothing reads after the last layer: the
-        # reference's autograd leaves their .grad None (and torch.optim.Adam then skips them); the kernels wrote zeros.
+        # reference's autograd leaves their .grad None (and torch.optim.Adam then skips them); the kernels wrote zeros (or, with the
+        # skip of _skip_last_node_update, nothing).
         if guard is not None:   # an overflowed forward (outputs non-finite) hands zero parameter gradients on, whenever the host learns of it
             guard.zero_if_flagged(lib, flat)
         last = spec.n_layers - 1

@@ -188,7 +188,10 @@ typedef struct {
   const float *x;          /* [N,3] */
   const float *Z;          /* [B,3,C]   virtual coordinates (reference layout) */
   const float *HvT;        /* [B,C,64]  virtual features, channel-major */
-  /* layer outputs */
+  /* layer outputs.  h_out == NULL && HvT_out == NULL (FastEGNN wiring, i.e. neither FASTEGNN_F_RF nor FASTEGNN_F_EGNN): the node update of
+   * this layer is not wanted -- node_model and node_model_virtual are not run (nothing reads h / Hv after the last layer of FastEGNN),
+   * x_out and Z_out are what they are otherwise; npre and poolV are then not written and may be null too.  Exactly one of the two null
+   * is FASTEGNN_E_INVALID (checked before any launch), as a null h_out is under the other two wirings. */
   float *h_out, *x_out, *Z_out, *HvT_out;
 
   /* stage products (saved for backward) */
@@ -205,7 +208,10 @@ typedef struct {
   float *poolV;            /* [B,C,64] S4 (sum over nodes; sharded: all-reduced) */
   float *poolX;            /* [B,3,C]  S4 (sum over nodes; sharded: all-reduced) */
 
-  /* backward inputs: d loss / d layer outputs */
+  /* backward inputs: d loss / d layer outputs.  g_h_out == NULL && g_HvT_out == NULL (FastEGNN wiring): no gradient arrives for h / Hv, and
+   * the forward of this layer ran without its node update (above) -- the adjoint of node_model / node_model_virtual is not run, grads[] of
+   * node_mlp.* and node_mlp_virtual.* are left untouched, npre, poolV and g_poolV are not read and may be null; g_h, g_x, g_Z, g_HvT
+   * and every other gradient are what a zero g_h_out / g_HvT_out gives.  Exactly one of the two null is FASTEGNN_E_INVALID. */
   const float *g_h_out, *g_x_out, *g_Z_out, *g_HvT_out;
   /* backward outputs: d loss / d layer inputs */
   float *g_h, *g_x, *g_Z, *g_HvT;
