@@ -122,6 +122,159 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   }
 }
 
+// workgroups per tensor of a multi-tensor launch over tensors of at most nmax elements (adam_kernel's grid)
+inline int adam_grid_x(long nmax) {
+  int gx = cdiv(nmax, 256 * 4);
+  return gx > 64 ? 64 : (gx < 1 ? 1 : gx);
+}
+
+// sum over the 256 threads of a workgroup in a FIXED order (xor butterfly within each wave, then ((w0 + w1) + (w2 + w3))); valid in thread 0
+__device__ inline double block_sum_f64(double s, double *red) {
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// ---- sum of squares of all gradients, stage 1: workgroup (x, t) of a launch writes the fp64 sum of its grid-stride share of
+// tensor t into its own slot part[t * gridDim.x + x] (0 for an absent gradient or a share that is empty).  fp32 x fp32 is exact in
+// fp64 and nothing clamps or compares, so an Inf / NaN element reaches the slot.  No atomics: the slot layout and the order of every
+// sum are fixed by the tensor sizes, which makes the result run-to-run identical.
+struct SqnArgs {
+  const float *g[ADAM_MAX];
+  long n[ADAM_MAX];
+  double *part;
+};
+__global__ __launch_bounds__(256) void grad_sqnorm_partial_kernel(SqnArgs a) {
+  __shared__ double red[4];
+  const int t = blockIdx.y;
+  const float *g = a.g[t];
+  double s = 0.0;
+  if (g) {
+    const long n = a.n[t], stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
+    long done = 0;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {   // 16-byte loads over the aligned body, scalar tail
+      const long n4 = n / 4;
+      const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
+      for (long i = first; i < n4; i += stride) {
+        const f32x4 x = g4[i];
+        s += (double)x[0] * (double)x[0];
+        s += (double)x[1] * (double)x[1];
+        s += (double)x[2] * (double)x[2];
+        s += (double)x[3] * (double)x[3];
+      }
+      done = 4 * n4;
+    }
+    for (long i = done + first; i < n; i += stride) s += (double)g[i] * (double)g[i];
+  }
+  s = block_sum_f64(s, red);
+  if (threadIdx.x == 0) a.part[(size_t)t * gridDim.x + blockIdx.x] = s;
+}
+// stage 2, ONE workgroup: thread i sums slots i, i + 256, ... in ascending order, then the fixed workgroup order
+__global__ __launch_bounds__(256) void grad_sqnorm_final_kernel(const double *part, long n, double *out) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) s += part[i];
+  s = block_sum_f64(s, red);
+  if (threadIdx.x == 0) *out = s;
+}
+
+// ---- Adam with its per-step state on the device (fastegnn_adam_step_dev).
+// The hazard: every workgroup of tensor t must see the SAME step count, so no workgroup of the element kernel may advance
+// steps_dev[t] while others still read it (and all of them must take the same skip decision, from a word that a host may clear at
+// any moment).  The simplest design that makes this impossible is stream order: a ONE-workgroup prologue launch reads the skip word
+// and the norm once, advances the counts, and writes everything the update needs -- apply flag, clip coefficient, the fp32
+// hyper-parameters, each tensor's lr_t and 1 / sqrt(bc2) -- into a scalar block; the element launches behind it on the stream read
+// that block and nothing else.  No grid-wide synchronisation, no atomics, one more (tiny) launch per step.
+// scalar block, fp32: [0] apply (1 / 0)  [1] clip  [2] b1  [3] b2  [4] 1 - b1  [5] 1 - b2  [6] eps  [7] wd  [8 + 2 t] lr_t  [9 + 2 t] 1 / sqrt(bc2)
+constexpr int ADAM_SC_HEAD = 8;
+constexpr int ADAM_PRO_MAX = 2048;   // tensors per prologue launch (their has-a-gradient bits travel in the launch arguments)
+struct AdamProArgs {
+  unsigned has[ADAM_PRO_MAX / 32];
+  int base, count, first;
+  int *steps;
+  const double *hyper, *sqnorm;
+  const volatile int *skip;
+  float *sc;
+};
+__global__ __launch_bounds__(256) void adam_dev_prologue_kernel(AdamProArgs a) {
+  __shared__ int apply_s;
+  const double lr = a.hyper[0], b1 = a.hyper[1], b2 = a.hyper[2];
+  if (threadIdx.x == 0) {
+    int apply = 1;
+    if (a.first) {   // the decision is taken ONCE per step: later prologue launches of the same step read it back
+      double clip = 1.0;
+      if (a.skip && *a.skip != 0) apply = 0;
+      if (a.sqnorm) {
+        const double sq = *a.sqnorm, max_norm = a.hyper[5];
+        if (!__builtin_isfinite(sq)) apply = 0;
+        else if (max_norm > 0.0) clip = fmin(1.0, max_norm / (sqrt(sq) + 1e-6));
+      }
+      a.sc[0] = apply ? 1.f : 0.f;
+      a.sc[1] = (float)clip;
+      a.sc[2] = (float)b1; a.sc[3] = (float)b2; a.sc[4] = (float)(1.0 - b1); a.sc[5] = (float)(1.0 - b2);
+      a.sc[6] = (float)a.hyper[3]; a.sc[7] = (float)a.hyper[4];
+    } else {
+      apply = a.sc[0] != 0.f;
+    }
+    apply_s = apply;
+  }
+  __syncthreads();
+  if (!apply_s) return;   // a skipped step: the counts stay
+  for (int t = threadIdx.x; t < a.count; t += 256) {
+    if (!(a.has[t >> 5] >> (t & 31) & 1u)) continue;   // no gradient: no step (torch.optim.Adam)
+    const int step = a.steps[a.base + t] + 1;
+    a.steps[a.base + t] = step;
+    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    a.sc[ADAM_SC_HEAD + 2 * (a.base + t)] = (float)(lr / bc1);
+    a.sc[ADAM_SC_HEAD + 2 * (a.base + t) + 1] = (float)(1.0 / sqrt(bc2));
+  }
+}
+
+struct AdamDevArgs {
+  float *p[ADAM_MAX], *m[ADAM_MAX], *v[ADAM_MAX];
+  const float *g[ADAM_MAX];
+  long n[ADAM_MAX];
+  int base;
+  const float *sc;
+};
+struct AdamCoef { float clip, b1, b2, omb1, omb2, eps, wd, lr_t, inv_bc2_sqrt; };
+__device__ inline void adam_element(float &p, float &m, float &v, float g, const AdamCoef &c) {
+  const float gi = g * c.clip + c.wd * p;
+  m = c.b1 * m + c.omb1 * gi;
+  v = c.b2 * v + c.omb2 * gi * gi;
+  p -= c.lr_t * m / (sqrtf(v) * c.inv_bc2_sqrt + c.eps);
+}
+__global__ __launch_bounds__(256) void adam_dev_kernel(AdamDevArgs a) {
+  const int t = blockIdx.y;
+  const float *g = a.g[t];
+  if (!g || a.sc[0] == 0.f) return;
+  float *p = a.p[t], *m = a.m[t], *v = a.v[t];
+  const float *sc = a.sc;
+  const AdamCoef c = {sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], sc[7],
+                      sc[ADAM_SC_HEAD + 2 * (a.base + t)], sc[ADAM_SC_HEAD + 2 * (a.base + t) + 1]};
+  const long n = a.n[t], stride = (long)gridDim.x * 256, first = (long)blockIdx.x * 256 + threadIdx.x;
+  long done = 0;
+  if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+        reinterpret_cast<uintptr_t>(g)) & 15) == 0) {   // 16-byte loads / stores over the aligned body, scalar tail
+    const long n4 = n / 4;
+    f32x4 *p4 = reinterpret_cast<f32x4 *>(p), *m4 = reinterpret_cast<f32x4 *>(m), *v4 = reinterpret_cast<f32x4 *>(v);
+    const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
+    for (long i = first; i < n4; i += stride) {
+      f32x4 pi = p4[i], mi = m4[i], vi = v4[i];
+      const f32x4 gi = g4[i];
+      for (int k = 0; k < 4; ++k) {
+        float pk = pi[k], mk = mi[k], vk = vi[k];
+        adam_element(pk, mk, vk, gi[k], c);
+        pi[k] = pk; mi[k] = mk; vi[k] = vk;
+      }
+      m4[i] = mi; v4[i] = vi; p4[i] = pi;
+    }
+    done = 4 * n4;
+  }
+  for (long i = done + first; i < n; i += stride) adam_element(p[i], m[i], v[i], g[i], c);
+}
+
 }  // namespace fe
 
 using namespace fe;
@@ -183,6 +336,87 @@ int fastegnn_adam_step_v2(float *const *params, const float *const *grads, float
     hipLaunchKernelGGL(adam_kernel, dim3(gx, a.count), dim3(256), 0, st, a);
   }
   return check_launch("adam_kernel");
+}
+
+size_t fastegnn_grad_sqnorm_partials(const int64_t *numel, int32_t n_tensors) {
+  if (!numel || n_tensors <= 0) return 1;
+  size_t slots = 0;
+  for (int base = 0; base < n_tensors; base += ADAM_MAX) {
+    const int count = n_tensors - base < ADAM_MAX ? n_tensors - base : ADAM_MAX;
+    long nmax = 0;
+    for (int t = 0; t < count; ++t) nmax = numel[base + t] > nmax ? numel[base + t] : nmax;
+    slots += (size_t)count * adam_grid_x(nmax);
+  }
+  return slots;
+}
+
+int fastegnn_grad_sqnorm(const float *const *grads, const int64_t *numel, int32_t n_tensors, double *ws,
+                         size_t ws_doubles, double *out, void *stream) {
+  FE_REQUIRE(grads && numel && ws && out && n_tensors >= 0, "grad_sqnorm: bad argument");
+  FE_REQUIRE(ws_doubles >= fastegnn_grad_sqnorm_partials(numel, n_tensors), "grad_sqnorm: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  size_t slot = 0;
+  for (int base = 0; base < n_tensors; base += ADAM_MAX) {
+    SqnArgs a;
+    const int count = n_tensors - base < ADAM_MAX ? n_tensors - base : ADAM_MAX;
+    long nmax = 0;
+    for (int t = 0; t < ADAM_MAX; ++t) {
+      a.g[t] = t < count ? grads[base + t] : nullptr;
+      a.n[t] = t < count ? numel[base + t] : 0;
+      FE_REQUIRE(a.n[t] >= 0, "grad_sqnorm: negative numel");
+      if (a.n[t] > nmax) nmax = a.n[t];
+    }
+    a.part = ws + slot;
+    const int gx = adam_grid_x(nmax);
+    hipLaunchKernelGGL(grad_sqnorm_partial_kernel, dim3(gx, count), dim3(256), 0, st, a);
+    slot += (size_t)count * gx;
+  }
+  hipLaunchKernelGGL(grad_sqnorm_final_kernel, dim3(1), dim3(256), 0, st, ws, (long)slot, out);
+  return check_launch("grad_sqnorm");
+}
+
+size_t fastegnn_adam_dev_scratch_bytes(int32_t n_tensors) {
+  return (size_t)(ADAM_SC_HEAD + 2 * (n_tensors > 0 ? n_tensors : 0)) * sizeof(float);
+}
+
+int fastegnn_adam_step_dev(float *const *params, const float *const *grads, float *const *exp_avg,
+                           float *const *exp_avg_sq, const int64_t *numel, int32_t n_tensors, int32_t *steps_dev,
+                           const double *hyper_dev, const double *sqnorm_dev, const int32_t *skip_word, void *scratch,
+                           size_t scratch_bytes, void *stream) {
+  FE_REQUIRE(params && grads && exp_avg && exp_avg_sq && numel && n_tensors >= 0, "adam_step_dev: bad argument");
+  FE_REQUIRE(steps_dev && hyper_dev && scratch, "adam_step_dev: the step counts, the hyper-parameters and the scratch block live in device memory");
+  FE_REQUIRE(scratch_bytes >= fastegnn_adam_dev_scratch_bytes(n_tensors) && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0,
+             "adam_step_dev: scratch too small or not 16-byte aligned");
+  for (int t = 0; t < n_tensors; ++t)
+    FE_REQUIRE(numel[t] >= 0 && (!grads[t] || (params[t] && exp_avg[t] && exp_avg_sq[t])), "adam_step_dev: null tensor");
+  hipStream_t st = (hipStream_t)stream;
+  float *sc = static_cast<float *>(scratch);
+  for (int base = 0; base < n_tensors || base == 0; base += ADAM_PRO_MAX) {   // (n_tensors = 0 still takes the decision: one launch)
+    AdamProArgs pa;
+    pa.base = base;
+    pa.count = n_tensors - base < ADAM_PRO_MAX ? n_tensors - base : ADAM_PRO_MAX;
+    pa.first = base == 0;
+    for (int w = 0; w < ADAM_PRO_MAX / 32; ++w) pa.has[w] = 0u;
+    for (int t = 0; t < pa.count; ++t)
+      if (grads[base + t]) pa.has[t >> 5] |= 1u << (t & 31);
+    pa.steps = steps_dev; pa.hyper = hyper_dev; pa.sqnorm = sqnorm_dev; pa.skip = skip_word; pa.sc = sc;
+    hipLaunchKernelGGL(adam_dev_prologue_kernel, dim3(1), dim3(256), 0, st, pa);
+  }
+  for (int base = 0; base < n_tensors; base += ADAM_MAX) {
+    AdamDevArgs a;
+    const int count = n_tensors - base < ADAM_MAX ? n_tensors - base : ADAM_MAX;
+    long nmax = 0;
+    for (int t = 0; t < ADAM_MAX; ++t) {
+      const bool in = t < count;
+      a.p[t] = in ? params[base + t] : nullptr; a.g[t] = in ? grads[base + t] : nullptr;
+      a.m[t] = in ? exp_avg[base + t] : nullptr; a.v[t] = in ? exp_avg_sq[base + t] : nullptr;
+      a.n[t] = in ? numel[base + t] : 0;
+      if (a.n[t] > nmax) nmax = a.n[t];
+    }
+    a.base = base; a.sc = sc;
+    hipLaunchKernelGGL(adam_dev_kernel, dim3(adam_grid_x(nmax), count), dim3(256), 0, st, a);
+  }
+  return check_launch("adam_step_dev");
 }
 
 // every tensor at the same step: the form of ABI revisions up to 107

@@ -58,21 +58,140 @@ def mse_mmd_loss(loc_pred, vloc, loc_t, sample_nodes, sigma, weight):
 
 
 class FusedAdam:
-    """``torch.optim.Adam(params, lr, weight_decay)`` semantics (main_nbody.py:137) as multi-tensor HIP launches."""
+    """``torch.optim.Adam(params, lr, weight_decay)`` semantics (main_nbody.py:137) as multi-tensor HIP launches.
 
-    def __init__(self, params: Iterable[torch.nn.Parameter], lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    ``capturable=True`` (as ``torch.optim.Adam(capturable=True)``): the step counts, the hyper-parameters and the decision to skip
+    live in DEVICE memory (fastegnn_adam_step_dev), so ``step()`` reads nothing back, synchronises nothing and may be captured
+    into a HIP graph whose replays then train:
+
+    * ``opt.lr = x`` / ``opt.set_lr(x)`` write the device buffer with a stream-ordered copy (outside a capture); the next replay
+      uses the new value, nothing is re-captured;
+    * ``opt.steps`` copies the counts back (one synchronisation: tests and checkpoints);
+    * ``opt.skip_word``: a device int32 tensor or the address of a device / host-mapped word; while the word is non-zero a step
+      moves NOTHING (parameters, moments, counts), a loss scaler's skipped step.  ``opt.attach_guard(model)`` uses the OUT word
+      of the model's RangeGuard for as long as the model runs on the f16x2 build: the step that follows an overflowed forward
+      is skipped on the device, whenever the host learns of it;
+    * ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_``'s coefficient, applied to the gradients as they are read (the
+      ``.grad`` buffers are not rewritten); a step whose gradient norm is not finite is skipped like one with a set word.
+
+    Which parameters have a gradient is read from ``p.grad`` when ``step()`` is CALLED: a captured step freezes that set (and the
+    gradient addresses) as they were at capture time.  The default ``capturable=False`` is the host-side path, unchanged."""
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 capturable=False, max_grad_norm=None):
+        if max_grad_norm is not None and not capturable:
+            raise ValueError("fastegnn_amd.FusedAdam: max_grad_norm needs capturable=True (the clipped step is the device-side one)")
+        self.capturable = bool(capturable)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._dev = None                       # device buffers of the capturable path (_ensure_device)
+        self._guard = None
+        self._skip_keep = None
+        self._skip_addr = None
         self.params = [p for p in params if p.requires_grad]
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self._lr = lr
+        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         self.exp_avg = [torch.zeros_like(p) for p in self.params]
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
         self.step_count = 0                    # calls of step()
         n = len(self.params)
         # torch.optim.Adam's state['step'] of each parameter: advanced only on the steps where it has a .grad, and its
         # bias correction follows its own count (a parameter first reached at step 2 is corrected as at step 1)
-        self.steps = [0] * n
+        self._steps = [0] * n
         self._numel = (C.c_int64 * n)(*[p.numel() for p in self.params])
         self._m = (C.c_void_p * n)(*[t.data_ptr() for t in self.exp_avg])
         self._v = (C.c_void_p * n)(*[t.data_ptr() for t in self.exp_avg_sq])
+        if self.capturable and self.params and self.params[0].is_cuda:
+            self._ensure_device(self.params[0].device)
+
+    # ---- state that lives on the device when capturable ----
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        self.set_lr(value)
+
+    def set_lr(self, value):
+        self._lr = float(value)
+        if self._dev is not None:
+            self._write_hyper()
+
+    @property
+    def steps(self):
+        """per-parameter step counts (capturable: copied back from the device, which synchronises)"""
+        if self.capturable and self._dev is not None:
+            return [int(v) for v in self._dev["steps"].tolist()]
+        return self._steps
+
+    @property
+    def skip_word(self):
+        return self._skip_keep if self._skip_keep is not None else self._skip_addr
+
+    @skip_word.setter
+    def skip_word(self, word):
+        if word is not None and not self.capturable:
+            raise ValueError("fastegnn_amd.FusedAdam: skip_word needs capturable=True")
+        self._skip_keep, self._skip_addr = None, None
+        if isinstance(word, torch.Tensor):
+            if word.dtype != torch.int32 or not word.is_cuda or word.numel() < 1:
+                raise ValueError("fastegnn_amd.FusedAdam: skip_word as a tensor must be an int32 tensor on the GPU")
+            self._skip_keep, self._skip_addr = word, word.data_ptr()
+        elif word is not None:
+            self._skip_addr = word.value if isinstance(word, C.c_void_p) else int(word)
+
+    def attach_guard(self, model):
+        """skip by the OUT word of ``model``'s RangeGuard (host-mapped; allocated by the model's first eager forward)"""
+        guard = getattr(model, "_range", None)
+        if guard is None or not self.capturable:
+            raise ValueError("fastegnn_amd.FusedAdam.attach_guard: needs capturable=True and a module with a range guard")
+        self._guard = guard
+
+    def _skip_ptr(self):
+        if self._skip_addr is not None:
+            return C.c_void_p(self._skip_addr)
+        guard = self._guard
+        # on the wide-range build no guard launch runs any more and the words are dead (OUT stays set after the switch)
+        if guard is None or guard.wide:
+            return None
+        if guard._words is None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fastegnn_amd.FusedAdam: the range guard's host-mapped words do not exist yet; run one eager forward "
+                               "of the module before capturing the step into a HIP graph")
+        return guard.word_ptr(guard.OUT)
+
+    def _write_hyper(self):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fastegnn_amd.FusedAdam: hyper-parameters are written between replays, not inside a stream capture")
+        h = [self._lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+             self.max_grad_norm if self.max_grad_norm is not None else 0.0]
+        self._dev["hyper"].copy_(torch.tensor(h, dtype=torch.float64))
+
+    def _ensure_device(self, dev):
+        d = self._dev
+        if d is not None and d["hyper"].device == dev:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fastegnn_amd.FusedAdam: build the capturable optimizer on the GPU parameters (or run one eager "
+                               "step) before capturing it")
+        n = len(self.params)
+        L = K.lib()
+        steps = torch.tensor(d["steps"].tolist() if d is not None else self._steps, dtype=torch.int32).reshape(n).to(dev)
+        self._dev = dict(
+            steps=steps, hyper=torch.zeros(6, dtype=torch.float64, device=dev),
+            sqnorm=torch.zeros(1, dtype=torch.float64, device=dev),
+            sqn_ws=torch.zeros(max(int(L.fastegnn_grad_sqnorm_partials(self._numel, n)), 1), dtype=torch.float64, device=dev),
+            scratch=torch.zeros((int(L.fastegnn_adam_dev_scratch_bytes(n)) + 3) // 4, dtype=torch.float32, device=dev))
+        self._write_hyper()
+
+    @property
+    def n_partials(self) -> int:
+        """workgroup partials the gradient-norm reduction sums (fastegnn_grad_sqnorm_partials)"""
+        return int(K.lib().fastegnn_grad_sqnorm_partials(self._numel, len(self.params)))
+
+    @property
+    def grad_sqnorm(self) -> torch.Tensor:
+        """the device scalar (fp64) the latest clipped step reduced the squared gradient norm into"""
+        return self._dev["sqnorm"]
 
     def zero_grad(self):
         for p in self.params:
@@ -87,8 +206,8 @@ class FusedAdam:
             if g is not None and (not g.is_contiguous() or g.dtype != torch.float32):
                 g = g.contiguous().float()
             grads.append(g)
-            if g is not None:
-                self.steps[len(grads) - 1] += 1
+            if g is not None and not self.capturable:
+                self._steps[len(grads) - 1] += 1
         gp = (C.c_void_p * n)(*[(g.data_ptr() if g is not None else None) for g in grads])
         dev = self.params[0].device
         # parameter pointers are read at every step: a model moved with .to() / .cuda() after the optimizer was built
@@ -98,16 +217,29 @@ class FusedAdam:
             if self.exp_avg[i].device != p.device:
                 self.exp_avg[i], self.exp_avg_sq[i] = self.exp_avg[i].to(p.device), self.exp_avg_sq[i].to(p.device)
                 self._m[i], self._v[i] = self.exp_avg[i].data_ptr(), self.exp_avg_sq[i].data_ptr()
-        steps = (C.c_int32 * n)(*self.steps)
+        if self.capturable:
+            return self._step_device(pp, gp, n, dev)
+        steps = (C.c_int32 * n)(*self._steps)
         K.check(K.lib().fastegnn_adam_step_v2(pp, gp, self._m, self._v, self._numel, n, steps,
                                               float(self.lr), float(self.betas[0]), float(self.betas[1]),
                                               float(self.eps), float(self.weight_decay), _stream(dev)),
                 "fastegnn_adam_step_v2")
 
+    def _step_device(self, pp, gp, n, dev):
+        """queue the device-side step: no host read, no synchronisation (legal inside a stream capture)"""
+        self._ensure_device(dev)
+        d, L, st = self._dev, K.lib(), _stream(dev)
+        clip = self.max_grad_norm is not None
+        if clip:
+            K.check(L.fastegnn_grad_sqnorm(gp, self._numel, n, K.ptr(d["sqn_ws"]), d["sqn_ws"].numel(), K.ptr(d["sqnorm"]), st),
+                    "fastegnn_grad_sqnorm")
+        K.check(L.fastegnn_adam_step_dev(pp, gp, self._m, self._v, self._numel, n, K.ptr(d["steps"]), K.ptr(d["hyper"]),
+                                         K.ptr(d["sqnorm"]) if clip else None, self._skip_ptr(), K.ptr(d["scratch"]),
+                                         d["scratch"].numel() * 4, st), "fastegnn_adam_step_dev")
 
-def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, weight):
-    """One iteration of utils/train.py:30-170 for the FastEGNN branch.  ``data`` holds the collated batch
-    (loc_0, vel_0, loc_t, node_feat, edge_index, edge_attr, batch, loc_mean) on the GPU.  Returns (loss, mse)."""
+
+def _forward_backward(model, optimizer, data: dict, sample_nodes, sigma, weight):
+    """augment + forward + MSE/MMD + backward of one iteration (everything of train_step in front of the optimizer)"""
     edge_attr = augment_edge_attr(data.get("edge_attr"), data["loc_0"], data["edge_index"])
     optimizer.zero_grad()
     loc_pred, vloc = model(node_loc=data["loc_0"], node_vel=data["vel_0"], node_attr=None,
@@ -115,11 +247,18 @@ def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, wei
                            data_batch=data["batch"], edge_attr=edge_attr)
     loss, mse = mse_mmd_loss(loc_pred, vloc, data["loc_t"], sample_nodes, sigma, weight)
     loss.backward()
+    return loss.detach(), mse
+
+
+def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, weight):
+    """One iteration of utils/train.py:30-170 for the FastEGNN branch.  ``data`` holds the collated batch
+    (loc_0, vel_0, loc_t, node_feat, edge_index, edge_attr, batch, loc_mean) on the GPU.  Returns (loss, mse)."""
+    loss, mse = _forward_backward(model, optimizer, data, sample_nodes, sigma, weight)
     # the range guard of the f16x2 build (fastegnn_amd.model.RangeGuard), polled without synchronisation: when THIS poll finds that a
     # pass left the fp16 operand range the module moves to the wide-range build and the update is skipped (its gradients were zeroed
     # on the device anyway), like a skipped step of a loss scaler
     guard = getattr(model, "_range", None)
     if guard is not None and guard.poll(type(model).__name__, getattr(model, "_plist", None), why="a training step"):
-        return loss.detach(), mse
+        return loss, mse
     optimizer.step()
-    return loss.detach(), mse
+    return loss, mse

@@ -252,6 +252,9 @@ const char *fastegnn_last_error(void);
  * round 5: fastegnn_f16_operands / fastegnn_check_finite: 105; the fused activation arguments of fastegnn_wide_linear / _dx / _dw: 106;
  * round 6: fastegnn_host_words_alloc / _free, fastegnn_zero_if_flagged, fastegnn_check_finite writes 1 instead of OR-ing: 107;
  * fastegnn_adam_step_v2 with a step count per tensor: 108).
+ * A purely ADDITIVE export -- a new function that leaves every descriptor and every existing argument as it was -- does not
+ * bump the revision: a binding finds it by symbol, and an older library fails that lookup (fastegnn_grad_sqnorm,
+ * fastegnn_adam_step_dev and their size queries were added at 108 this way).
  * A binding MUST compare it with the FASTEGNN_ABI_VERSION it was written against AND check fastegnn_sizeof_layer() /
  * fastegnn_sizeof_graph() against its own mirror of the descriptors before the first call (fastegnn_amd/_lib.py does). */
 #define FASTEGNN_ABI_VERSION 108
@@ -414,6 +417,39 @@ int fastegnn_adam_step_v2(float *const *params, const float *const *grads, float
 int fastegnn_adam_step(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                        const int64_t *numel, int32_t n_tensors, int32_t step, float lr, float beta1, float beta2,
                        float eps, float weight_decay, void *stream);
+
+/* ---- capturable optimizer step: every per-step quantity lives in DEVICE memory, so that a captured HIP graph that holds
+ * these launches can be replayed for every training iteration (torch.optim.Adam(capturable=True)).
+ * ADDITIVE exports: they change no descriptor and no existing argument, so FASTEGNN_ABI_VERSION stays 108 -- a binding
+ * finds them by symbol (fastegnn_amd/_lib.py lists them in EXPORTED; a library without them fails that lookup loudly).
+ *
+ * Sum of squares over all present gradients (HOST arrays of device pointers as for fastegnn_adam_step_v2; a null entry
+ * contributes nothing), written as ONE double to *out (device).  Two stages, no atomics: every workgroup writes its
+ * fp64 partial into `ws` (fastegnn_grad_sqnorm_partials(numel, n) doubles: the slot of a workgroup is fixed by the tensor
+ * sizes alone, not by which gradients are present), then one workgroup sums the slots in a fixed order -- run-to-run
+ * identical, capturable.  Every product is exact (fp32 x fp32 in fp64); a non-finite element gives a non-finite *out. */
+size_t fastegnn_grad_sqnorm_partials(const int64_t *numel, int32_t n_tensors);
+int fastegnn_grad_sqnorm(const float *const *grads, const int64_t *numel, int32_t n_tensors, double *ws,
+                         size_t ws_doubles, double *out, void *stream);
+/* fastegnn_adam_step_v2 with its per-step state on the device:
+ *   steps_dev  int32 [n_tensors], DEVICE: each tensor's step count, read AND advanced by this call;
+ *   hyper_dev  double [6], DEVICE: lr, beta1, beta2, eps, weight_decay, max_grad_norm (<= 0: no clipping);
+ *   sqnorm_dev double, DEVICE, may be null: fastegnn_grad_sqnorm's result (required when max_grad_norm > 0 is wanted:
+ *              without it no clipping happens);
+ *   skip_word  int32, device OR host-mapped (fastegnn_host_words_alloc), may be null: the range guard's word;
+ *   scratch    fastegnn_adam_dev_scratch_bytes(n_tensors) bytes, DEVICE, 16-byte aligned: written and read by this call only.
+ * If *skip_word != 0, or *sqnorm_dev is not finite, NOTHING moves: parameters, moments and steps_dev stay bitwise as they
+ * were (a loss scaler's skipped step).  Otherwise every tensor with a non-null gradient advances its count by one and takes
+ * torch.optim.Adam's update with the bias correction of its OWN new count, formed in fp64 on the device; with clipping
+ * each gradient is multiplied by min(1, max_grad_norm / (sqrt(*sqnorm_dev) + 1e-6)) as it is read
+ * (torch.nn.utils.clip_grad_norm_'s coefficient; the gradient buffers are not rewritten).  A tensor with a null
+ * gradient is untouched.  One single-workgroup prologue launch takes the decision and advances the counts; the element
+ * launches that follow on the stream read only what it wrote into `scratch`. */
+size_t fastegnn_adam_dev_scratch_bytes(int32_t n_tensors);
+int fastegnn_adam_step_dev(float *const *params, const float *const *grads, float *const *exp_avg,
+                           float *const *exp_avg_sq, const int64_t *numel, int32_t n_tensors, int32_t *steps_dev,
+                           const double *hyper_dev, const double *sqnorm_dev, const int32_t *skip_word, void *scratch,
+                           size_t scratch_bytes, void *stream);
 
 /* ---- graph construction on device (datasets/simulation/dataset.py:80,96-101) ----
  * radius graph without self loops: all ordered pairs (i, j != i) with |x_i - x_j|^2 <= r^2 (fp32, each
