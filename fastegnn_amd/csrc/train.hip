@@ -40,9 +40,11 @@ __global__ __launch_bounds__(256) void loss_mse_kernel(const float *pred, const 
 
 // MMD part, one workgroup per graph: l_vv = sum_{c,c'} k(V_c,V_c') / (B C^2), l_rv = 2 sum_{s,c} k(R_s,V_c) / (B S C),
 // k(x,y) = exp(-||x-y|| / (2 sigma^2));  loss[0] += weight (l_vv - l_rv);  gradients into g_vloc [B,3,C] and g_loc.
-__global__ __launch_bounds__(256) void loss_mmd_kernel(const float *pred, const float *vloc, const int32_t *samp, int B,
-                                                       int C, int S, float sigma, float weight, float *g_loc,
-                                                       float *g_vloc, float *loss) {
+// cnt (may be null: every row full): row b of samp holds cnt[b] <= S valid entries and only those are staged, paired and scattered;
+// l_rv keeps the divisor B S C (utils/train.py:142).  The LDS layout stays the one of S rows.
+__global__ __launch_bounds__(256) void loss_mmd_kernel(const float *pred, const float *vloc, const int32_t *samp,
+                                                       const int32_t *cnt, int B, int C, int S, float sigma, float weight,
+                                                       float *g_loc, float *g_vloc, float *loss) {
   extern __shared__ float sm[];
   float *V = sm;             // [C][3]
   float *gV = sm + 3 * C;    // [C][3]
@@ -50,13 +52,15 @@ __global__ __launch_bounds__(256) void loss_mmd_kernel(const float *pred, const 
   float *gR = R + 3 * S;     // [S][3]
   __shared__ float acc;
   const int b = blockIdx.x;
+  int Sb = cnt ? cnt[b] : S;
+  Sb = Sb < 0 ? 0 : (Sb > S ? S : Sb);   // documented in the header: the staging below must stay inside the S rows of LDS
   const float i2s = 1.0f / (2.f * sigma * sigma);
   for (int i = threadIdx.x; i < 3 * C; i += 256) {
     int c = i / 3, k = i % 3;
     V[i] = vloc[((size_t)b * 3 + k) * C + c];
     gV[i] = 0.f;
   }
-  for (int i = threadIdx.x; i < 3 * S; i += 256) {
+  for (int i = threadIdx.x; i < 3 * Sb; i += 256) {
     int s = i / 3, k = i % 3;
     R[i] = pred[(size_t)samp[b * S + s] * 3 + k];
     gR[i] = 0.f;
@@ -65,7 +69,7 @@ __global__ __launch_bounds__(256) void loss_mmd_kernel(const float *pred, const 
   __syncthreads();
   const float w_vv = weight / ((float)B * C * C), w_rv = -2.f * weight / ((float)B * S * C);
   float part = 0.f;
-  for (int i = threadIdx.x; i < C * C + S * C; i += 256) {
+  for (int i = threadIdx.x; i < C * C + Sb * C; i += 256) {
     const bool vv = i < C * C;
     const int a = vv ? i / C : (i - C * C) / C, c = vv ? i % C : (i - C * C) % C;
     const float *xa = vv ? V + 3 * a : R + 3 * a;
@@ -88,10 +92,63 @@ __global__ __launch_bounds__(256) void loss_mmd_kernel(const float *pred, const 
     int c = i / 3, k = i % 3;
     g_vloc[((size_t)b * 3 + k) * C + c] = gV[i];
   }
-  for (int i = threadIdx.x; i < 3 * S; i += 256) {
+  for (int i = threadIdx.x; i < 3 * Sb; i += 256) {
     int s = i / 3, k = i % 3;
     atomicAdd(&g_loc[(size_t)samp[b * S + s] * 3 + k], gR[i]);
   }
+}
+
+// ---- the device-side MMD sample (fastegnn_mmd_sample; the permutation is defined in include/fastegnn_hip.h, integers only) ----
+__host__ __device__ inline uint64_t mix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ inline uint32_t mix32(uint32_t x) {
+  x ^= x >> 16; x *= 0x7FEB352Du;
+  x ^= x >> 15; x *= 0x846CA68Bu;
+  return x ^ (x >> 16);
+}
+constexpr int MMD_ROUNDS = 8;
+// One thread per entry (b, j), grid-stride; thread i < B also writes sample_count[i].  Reads rng and ptr, writes its own outputs:
+// no atomics, and every workgroup sees the same counter because nothing in this launch writes it (mmd_advance_kernel does, behind).
+__global__ __launch_bounds__(256) void mmd_sample_kernel(const int64_t *ptr, int B, int S, const uint64_t *rng, int32_t *nodes,
+                                                         int32_t *count) {
+  const long total = (long)B * S, stride = (long)gridDim.x * 256;
+  const uint64_t gkey = mix64(mix64(rng[0]) ^ rng[1]);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total || i < B; i += stride) {
+    if (i < B) {
+      const int64_t n = ptr[i + 1] - ptr[i];
+      count[i] = n < 0 ? 0 : (n < S ? (int32_t)n : S);
+    }
+    if (i >= total) continue;
+    const int b = (int)(i / S), j = (int)(i % S);
+    const int64_t p0 = ptr[b], n = ptr[b + 1] - p0;
+    if (j >= n) { nodes[i] = -1; continue; }
+    if (n <= S) { nodes[i] = (int32_t)(p0 + j); continue; }
+    int k = 64 - __builtin_clzll((unsigned long long)(n - 1));   // ceil(log2 n), n >= 2 here
+    if (k < 2) k = 2;
+    k += k & 1;
+    const int h = k >> 1;
+    const uint64_t mask = (1ull << h) - 1, g = mix64(gkey ^ (uint64_t)b);
+    uint64_t key[MMD_ROUNDS];
+    for (int r = 0; r < MMD_ROUNDS; ++r) key[r] = mix64(g + (uint64_t)r);
+    uint64_t x = (uint64_t)j;
+    // cycle walking: E is a bijection of [0, 2^k) and j < n, so the walk stays on j's own cycle, which holds at most 2^k - n values
+    // >= n -- it ends within 2^k - n + 1 applications (2^k / n < 4 on average)
+    do {
+      for (int r = 0; r < MMD_ROUNDS; ++r) {
+        const uint64_t L = x >> h, R = x & mask;
+        const uint64_t F = (uint64_t)(mix32((uint32_t)R ^ (uint32_t)key[r]) ^ (uint32_t)(key[r] >> 32)) & mask;
+        x = (R << h) | (L ^ F);
+      }
+    } while (x >= (uint64_t)n);
+    nodes[i] = (int32_t)(p0 + (int64_t)x);
+  }
+}
+__global__ void mmd_advance_kernel(uint64_t *rng) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) rng[1] += 1;
 }
 
 // torch.optim.Adam (no amsgrad; weight decay folded into the gradient), up to 24 tensors per launch.  Each tensor carries its
@@ -290,9 +347,10 @@ int fastegnn_augment_edge_attr(const int64_t *edge_index, const float *loc, cons
   return check_launch("augment_edge_attr_kernel");
 }
 
-int fastegnn_loss_mse_mmd(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
-                          int32_t N, int32_t B, int32_t C, int32_t S, float sigma, float weight, float *loss2,
-                          float *g_loc, float *g_vloc, void *stream) {
+// both loss entry points: sample_count null = every row of sample_nodes is full
+static int loss_mse_mmd_launch(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                               const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
+                               float weight, float *loss2, float *g_loc, float *g_vloc, void *stream) {
   FE_REQUIRE(loc_pred && loc_t && vloc && loss2 && g_loc && g_vloc && (S == 0 || sample_nodes),
              "loss_mse_mmd: null pointer");
   FE_REQUIRE(C <= 256 && S <= 4096, "loss_mse_mmd: C <= 256 and S <= 4096");
@@ -303,9 +361,40 @@ int fastegnn_loss_mse_mmd(const float *loc_pred, const float *loc_t, const float
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(loss_mse_kernel, dim3(grid), dim3(256), 0, st, loc_pred, loc_t, (long)N * 3, g_loc, loss2);
   const size_t lds = (size_t)(6 * C + 6 * S) * sizeof(float);
-  hipLaunchKernelGGL(loss_mmd_kernel, dim3(B), dim3(256), lds, st, loc_pred, vloc, sample_nodes, B, C, S, sigma, weight,
-                     g_loc, g_vloc, loss2);
+  if (B > 0)   // no graph, no MMD term (and no launch of an empty grid)
+    hipLaunchKernelGGL(loss_mmd_kernel, dim3(B), dim3(256), lds, st, loc_pred, vloc, sample_nodes, sample_count, B, C, S, sigma,
+                       weight, g_loc, g_vloc, loss2);
   return check_launch("loss_mse_mmd");
+}
+
+int fastegnn_loss_mse_mmd(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                          int32_t N, int32_t B, int32_t C, int32_t S, float sigma, float weight, float *loss2,
+                          float *g_loc, float *g_vloc, void *stream) {
+  return loss_mse_mmd_launch(loc_pred, loc_t, vloc, sample_nodes, nullptr, N, B, C, S, sigma, weight, loss2, g_loc, g_vloc,
+                             stream);
+}
+
+int fastegnn_loss_mse_mmd_ragged(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                                 const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
+                                 float weight, float *loss2, float *g_loc, float *g_vloc, void *stream) {
+  FE_REQUIRE(sample_count || B == 0, "loss_mse_mmd_ragged: null sample_count (fastegnn_loss_mse_mmd is the form with full rows)");
+  return loss_mse_mmd_launch(loc_pred, loc_t, vloc, sample_nodes, sample_count, N, B, C, S, sigma, weight, loss2, g_loc,
+                             g_vloc, stream);
+}
+
+int fastegnn_mmd_sample(const int64_t *ptr, int32_t B, int32_t S, uint64_t *rng, int32_t advance, int32_t *sample_nodes,
+                        int32_t *sample_count, void *stream) {
+  FE_REQUIRE(B >= 0 && S >= 0 && S <= 4096, "mmd_sample: B >= 0 and 0 <= S <= 4096");
+  FE_REQUIRE(ptr && rng && (B == 0 || sample_count) && (B == 0 || S == 0 || sample_nodes), "mmd_sample: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (B > 0) {
+    const long total = (long)B * S > B ? (long)B * S : B;
+    long grid = (total + 255) / 256;
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(mmd_sample_kernel, dim3((unsigned)grid), dim3(256), 0, st, ptr, B, S, rng, sample_nodes, sample_count);
+  }
+  if (advance) hipLaunchKernelGGL(mmd_advance_kernel, dim3(1), dim3(1), 0, st, rng);
+  return check_launch("mmd_sample");
 }
 
 int fastegnn_adam_step_v2(float *const *params, const float *const *grads, float *const *exp_avg,

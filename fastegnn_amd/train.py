@@ -30,16 +30,24 @@ def augment_edge_attr(edge_attr: Optional[torch.Tensor], loc_0: torch.Tensor, ed
 
 class _MseMmd(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loc_pred, vloc, loc_t, sample_nodes, sigma, weight):
+    def forward(ctx, loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count=None):
         dev = loc_pred.device
         loc_pred, vloc, loc_t = loc_pred.contiguous().float(), vloc.contiguous().float(), loc_t.contiguous().float()
         N, (B, _, Cn), S = loc_pred.size(0), vloc.shape, sample_nodes.size(1)
         loss2 = torch.empty(2, dtype=torch.float32, device=dev)
         g_loc, g_vloc = torch.empty_like(loc_pred), torch.empty_like(vloc)
-        samp = sample_nodes.to(torch.int32).contiguous()
-        K.check(K.lib().fastegnn_loss_mse_mmd(K.ptr(loc_pred), K.ptr(loc_t), K.ptr(vloc), K.ptr(samp), N, B, Cn, S,
-                                              float(sigma), float(weight), K.ptr(loss2), K.ptr(g_loc), K.ptr(g_vloc),
-                                              _stream(dev)), "fastegnn_loss_mse_mmd")
+        samp = sample_nodes.to(torch.int32).contiguous()          # no copy when it is int32 and contiguous already
+        if sample_count is None:
+            K.check(K.lib().fastegnn_loss_mse_mmd(K.ptr(loc_pred), K.ptr(loc_t), K.ptr(vloc), K.ptr(samp), N, B, Cn, S,
+                                                  float(sigma), float(weight), K.ptr(loss2), K.ptr(g_loc), K.ptr(g_vloc),
+                                                  _stream(dev)), "fastegnn_loss_mse_mmd")
+        else:
+            if sample_count.numel() != B:
+                raise ValueError(f"fastegnn_amd.mse_mmd_loss: sample_count has {sample_count.numel()} entries for {B} graphs")
+            cnt = sample_count.to(torch.int32).contiguous()
+            K.check(K.lib().fastegnn_loss_mse_mmd_ragged(K.ptr(loc_pred), K.ptr(loc_t), K.ptr(vloc), K.ptr(samp), K.ptr(cnt),
+                                                         N, B, Cn, S, float(sigma), float(weight), K.ptr(loss2), K.ptr(g_loc),
+                                                         K.ptr(g_vloc), _stream(dev)), "fastegnn_loss_mse_mmd_ragged")
         ctx.save_for_backward(g_loc, g_vloc)
         ctx.mark_non_differentiable(loss2)
         return loss2[0], loss2
@@ -47,14 +55,102 @@ class _MseMmd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g2):
         g_loc, g_vloc = ctx.saved_tensors
-        return g * g_loc, g * g_vloc, None, None, None, None
+        return g * g_loc, g * g_vloc, None, None, None, None, None
 
 
-def mse_mmd_loss(loc_pred, vloc, loc_t, sample_nodes, sigma, weight):
+def mse_mmd_loss(loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count=None):
     """-> (loss, mse): ``MSE(loc_pred, loc_t) + weight * (l_vv - l_rv)`` and the plain MSE the harness logs
-    (utils/train.py:104-107,163-165).  ``sample_nodes`` [B,S]: absolute indices of the sampled real nodes."""
-    loss, loss2 = _MseMmd.apply(loc_pred, vloc, loc_t, sample_nodes, sigma, weight)
+    (utils/train.py:104-107,163-165).  ``sample_nodes`` [B,S]: absolute indices of the sampled real nodes.
+    ``sample_count`` int32 [B] (``MMDSampler.draw``'s second result): row b holds that many valid entries and the rest is never read
+    -- a graph smaller than the sample contributes all its nodes while l_rv keeps the divisor ``B * S * C``, as the reference's
+    variable-size branch does (utils/train.py:121-142).  ``None``: every row is full."""
+    loss, loss2 = _MseMmd.apply(loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count)
     return loss, loss2[1]
+
+
+def _u64(v):
+    return int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+def _i64(v):
+    v = _u64(v)
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+class MMDSampler:
+    """The reference's per-graph ``torch.randperm(n_i)[:num_sample]`` (utils/train.py:130) drawn on the device (fastegnn_mmd_sample):
+    a counter-based keyed permutation, so a draw is a function of ``(seed, counter, graph, position)`` alone.  ``seed`` and the draw
+    ``counter`` live in device memory (two uint64); ``draw`` reads them there and a launch behind it advances the counter, so replays
+    of a captured ``draw`` keep drawing fresh samples.  The output buffers are reused while ``(B, S)`` stay the same (a captured draw
+    keeps its addresses; the next draw overwrites them).  A draw with another ``(B, S)`` makes new buffers and the sampler lets go of
+    the old ones: a captured draw pins its ``(B, S)``, and whoever replays it keeps the tensors that ``draw`` returned during the
+    capture alive for as long as the graph is, or uses one sampler per captured shape."""
+
+    def __init__(self, seed, device=None):
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("fastegnn_amd.MMDSampler: the sample is drawn by a HIP kernel; there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fastegnn_amd.MMDSampler: build the sampler before the stream capture")
+        self.device = dev
+        self._state = torch.tensor([_i64(seed), 0], dtype=torch.int64).to(dev)   # the bit patterns of {seed, counter}
+        self._nodes = self._count = None
+
+    def _read(self, i):
+        return _u64(self._state[i].item())
+
+    def _write(self, i, value):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fastegnn_amd.MMDSampler: seed and counter are written between replays, not inside a stream capture")
+        self._state[i:i + 1].copy_(torch.tensor([_i64(value)], dtype=torch.int64))
+
+    @property
+    def seed(self):
+        """(reading copies the word back: one synchronisation)"""
+        return self._read(0)
+
+    @seed.setter
+    def seed(self, value):
+        self._write(0, value)
+
+    @property
+    def counter(self):
+        """draws taken with ``advance=True`` so far (reading copies the word back: one synchronisation)"""
+        return self._read(1)
+
+    @counter.setter
+    def counter(self, value):
+        self._write(1, value)
+
+    def state_dict(self):
+        seed, counter = self._state.tolist()
+        return {"seed": _u64(seed), "counter": _u64(counter)}
+
+    def load_state_dict(self, state):
+        self.seed, self.counter = state["seed"], state["counter"]
+
+    def draw(self, ptr, S, advance=True):
+        """``ptr``: the batch's ``data['ptr']`` (int64 [B+1] on the device) -> ``(sample_nodes int32 [B,S], sample_count int32 [B])``:
+        ``min(S, n_b)`` distinct nodes of every graph, the rest of a row -1.  Allocates nothing and reads nothing back once the
+        buffers of this ``(B, S)`` exist.  The two tensors are the sampler's own buffers: the next draw of the same ``(B, S)`` overwrites
+        them, and a draw of another ``(B, S)`` replaces them (a graph that captured this draw still writes the ones returned here, so
+        keep them alive with the graph)."""
+        if not (isinstance(ptr, torch.Tensor) and ptr.is_cuda and ptr.dtype == torch.int64 and ptr.dim() == 1 and ptr.numel() >= 1):
+            raise RuntimeError("fastegnn_amd.MMDSampler.draw: ptr must be the int64 [B+1] graph offsets on the GPU (no CPU fallback)")
+        if ptr.device != self.device:
+            raise RuntimeError(f"fastegnn_amd.MMDSampler.draw: ptr lives on {ptr.device}, the sampler on {self.device}")
+        B, S = ptr.numel() - 1, int(S)
+        if self._nodes is None or tuple(self._nodes.shape) != (B, S):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("fastegnn_amd.MMDSampler: the output buffers of this (B, S) do not exist yet; run one eager "
+                                   "draw (advance=False leaves the counter) before capturing it")
+            self._nodes = torch.full((B, S), -1, dtype=torch.int32, device=self.device)
+            self._count = torch.zeros(B, dtype=torch.int32, device=self.device)
+        K.check(K.lib().fastegnn_mmd_sample(K.ptr(ptr.contiguous()), B, S, K.ptr(self._state), 1 if advance else 0,
+                                            K.ptr(self._nodes), K.ptr(self._count), _stream(self.device)), "fastegnn_mmd_sample")
+        return self._nodes, self._count
 
 
 class FusedAdam:
@@ -238,22 +334,32 @@ class FusedAdam:
                                          d["scratch"].numel() * 4, st), "fastegnn_adam_step_dev")
 
 
-def _forward_backward(model, optimizer, data: dict, sample_nodes, sigma, weight):
+def _forward_backward(model, optimizer, data: dict, sample_nodes, sigma, weight, sample_count=None):
     """augment + forward + MSE/MMD + backward of one iteration (everything of train_step in front of the optimizer)"""
     edge_attr = augment_edge_attr(data.get("edge_attr"), data["loc_0"], data["edge_index"])
     optimizer.zero_grad()
     loc_pred, vloc = model(node_loc=data["loc_0"], node_vel=data["vel_0"], node_attr=None,
                            node_feat=data["node_feat"], edge_index=data["edge_index"], loc_mean=data["loc_mean"],
                            data_batch=data["batch"], edge_attr=edge_attr)
-    loss, mse = mse_mmd_loss(loc_pred, vloc, data["loc_t"], sample_nodes, sigma, weight)
+    loss, mse = mse_mmd_loss(loc_pred, vloc, data["loc_t"], sample_nodes, sigma, weight, sample_count)
     loss.backward()
     return loss.detach(), mse
 
 
-def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, weight):
+def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, weight, *, sampler: Optional[MMDSampler] = None,
+               num_sample: Optional[int] = None):
     """One iteration of utils/train.py:30-170 for the FastEGNN branch.  ``data`` holds the collated batch
-    (loc_0, vel_0, loc_t, node_feat, edge_index, edge_attr, batch, loc_mean) on the GPU.  Returns (loss, mse)."""
-    loss, mse = _forward_backward(model, optimizer, data, sample_nodes, sigma, weight)
+    (loc_0, vel_0, loc_t, node_feat, edge_index, edge_attr, batch, loc_mean) on the GPU.  Returns (loss, mse).
+    With ``sampler`` (and ``sample_nodes=None``) the step draws its own sample on the device: ``min(num_sample, N)`` nodes per graph
+    from ``data['ptr']`` (utils/train.py:116-130), a smaller graph all of its nodes, and the loss takes the per-graph counts."""
+    sample_count = None
+    if sampler is not None and sample_nodes is None:
+        if num_sample is None:
+            raise ValueError("fastegnn_amd.train_step: a sampler needs num_sample (the reference's sample * C)")
+        sample_nodes, sample_count = sampler.draw(data["ptr"], min(int(num_sample), data["loc_0"].size(0)))
+    elif sample_nodes is None:
+        raise ValueError("fastegnn_amd.train_step: sample_nodes is None and there is no sampler to draw them")
+    loss, mse = _forward_backward(model, optimizer, data, sample_nodes, sigma, weight, sample_count)
     # the range guard of the f16x2 build (fastegnn_amd.model.RangeGuard), polled without synchronisation: when THIS poll finds that a
     # pass left the fp16 operand range the module moves to the wide-range build and the update is skipped (its gradients were zeroed
     # on the device anyway), like a skipped step of a loss scaler

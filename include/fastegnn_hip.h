@@ -451,6 +451,45 @@ int fastegnn_adam_step_dev(float *const *params, const float *const *grads, floa
                            const double *hyper_dev, const double *sqnorm_dev, const int32_t *skip_word, void *scratch,
                            size_t scratch_bytes, void *stream);
 
+/* ---- the device-side MMD sample (utils/train.py:118-142: one torch.randperm(n_i)[:num_sample] per graph and step) ----
+ * ADDITIVE exports, found by symbol like the ones above: FASTEGNN_ABI_VERSION stays 108.
+ *
+ *   rng  DEVICE uint64[2] = {seed, draw counter};  ptr  DEVICE int64 [B+1], ascending (the collate's data['ptr']).
+ * For graph b with n = ptr[b+1] - ptr[b] (< 2^31):  sample_count[b] = min(S, n);
+ *   n <= S : sample_nodes[b, j] = ptr[b] + j            for j < n
+ *   n >  S : sample_nodes[b, j] = ptr[b] + perm_b(j)    for j < S, perm_b a keyed bijection of [0, n)
+ * and the entries j >= sample_count[b] of row b are written as -1.  sample_nodes int32 [B,S], sample_count int32 [B].
+ * advance != 0: a stream-ordered one-thread launch BEHIND the draw adds 1 to rng[1]; the draw itself only reads rng, so every
+ * workgroup of one draw sees the same counter.  B == 0 launches no draw; S == 0 writes only the counts (all 0); both still
+ * advance.  FASTEGNN_E_INVALID before any launch for: null rng / ptr, null sample_nodes with B * S > 0, null sample_count
+ * with B > 0, B < 0, S < 0, S > 4096 (the loss's ceiling).  Capturable: replays of a captured draw read the counter the previous
+ * replay left, so every replay draws a fresh sample.
+ *
+ * perm_b, in unsigned integer arithmetic only (uint64 sums and products wrap; a test mirrors it bit for bit):
+ *   mix64(x):  z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *              return z ^ (z >> 31)                                                   (splitmix64's output function)
+ *   mix32(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16   (uint32, products wrap)
+ *   k    = max(2, ceil(log2 n)) rounded up to even;  h = k / 2;  mask = 2^h - 1      (the domain 2^k is below 4 n for n >= 2)
+ *   g    = mix64(mix64(mix64(seed) ^ counter) ^ (uint64) b)
+ *   key_r = mix64(g + r),  r = 0 .. 7
+ *   E(x): for r = 0 .. 7:  L = x >> h;  R = x & mask;  F = (mix32((uint32) R ^ (uint32) key_r) ^ (uint32)(key_r >> 32)) & mask;
+ *                          x = (R << h) | (L ^ F)                                     (a balanced Feistel network: a bijection of [0, 2^k))
+ *   perm_b(j):  x = E(j);  while x >= n: x = E(x);  return x                          (cycle walking)
+ * E is a bijection, so perm_b is one of [0, n) and the S entries of a row are distinct.  The walk from a start below n stays on
+ * the start's own cycle of E, which holds at most 2^k - n values >= n: it ends within 2^k - n + 1 applications (about
+ * 2^k / n < 4 on average).  One thread per entry, no memory traffic besides ptr and the outputs, no atomics. */
+int fastegnn_mmd_sample(const int64_t *ptr, int32_t B, int32_t S, uint64_t *rng, int32_t advance, int32_t *sample_nodes,
+                        int32_t *sample_count, void *stream);
+/* fastegnn_loss_mse_mmd where row b of sample_nodes [B,S] holds sample_count[b] <= S valid entries (the rest is never read):
+ * a graph smaller than the sample contributes all its nodes, and l_rv is divided by B * S * C whatever the counts, as the
+ * reference's variable-size branch does (utils/train.py:142).  A count of 0 contributes to l_vv only.  sample_count int32 [B],
+ * DEVICE, must not be null unless B == 0, where nothing reads it (fastegnn_loss_mse_mmd is the form with every row full).  The
+ * counts are trusted like the indices: the valid entries of a row are not range-checked.  The one thing the kernel does with a
+ * count outside [0, S] is to read it as 0 or S, because a workgroup's LDS holds S rows. */
+int fastegnn_loss_mse_mmd_ragged(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                                 const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
+                                 float weight, float *loss2, float *g_loc, float *g_vloc, void *stream);
+
 /* ---- graph construction on device (datasets/simulation/dataset.py:80,96-101) ----
  * radius graph without self loops: all ordered pairs (i, j != i) with |x_i - x_j|^2 <= r^2 (fp32, each
  * operation rounded separately), grouped by i with j ascending.  Two passes so that the caller allocates:
