@@ -197,6 +197,7 @@ class EGNN(nn.Module):
             self.layers.append(EGNN_Layer(in_edge_nf, hidden_nf, activation, with_v, flat))
         self._spec = None
         self._graph_cache = {}
+        self.cache_graphs = True     # False: the CSR is built on every call (a captured HIP graph whose edge contents change between replays)
         self._range = RangeGuard()   # automatic wide-range fallback (fastegnn_amd.model.RangeGuard)
         self.deterministic = bool(K.deterministic_default())   # see fastegnn_amd.FastEGNN.deterministic (set before the first call)
         self.to(device)
@@ -238,13 +239,14 @@ class EGNN(nn.Module):
             self._build_spec()
         N = x.size(0)
         key = (edge_index.data_ptr(), edge_index.size(1), edge_index._version, N)
-        graph = self._graph_cache.get(key)
+        graph = self._graph_cache.get(key) if self.cache_graphs else None
         if graph is None:
             graph = SortedGraph(edge_index, N, csc=bool(self._spec.flags & K.F_DETERMINISTIC))
-            graph._keepalive = edge_index
-            if len(self._graph_cache) >= 8:
-                self._graph_cache.pop(next(iter(self._graph_cache)))
-            self._graph_cache[key] = graph
+            if self.cache_graphs:
+                graph._keepalive = edge_index
+                if len(self._graph_cache) >= 8:
+                    self._graph_cache.pop(next(iter(self._graph_cache)))
+                self._graph_cache[key] = graph
         if edge_fea is not None and edge_fea.size(1) == 0:
             edge_fea = None
         vv = v if v is not None else torch.zeros_like(x)

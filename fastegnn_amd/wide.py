@@ -407,7 +407,16 @@ def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_me
     idx_n = torch.arange(N, device=dev).repeat_interleave(C)                       # row n*C + c -> n
     col_sorted, col_perm = torch.sort(col, stable=True)          # once per graph: the column sums of every layer's backward as runs
     col_order = (col_sorted, col_perm)
-    gravity = torch.tensor(model.gravity, **ones) if model.gravity is not None else None
+    gravity = None
+    if model.gravity is not None:
+        # kept on the device between calls: torch.tensor(list, device=cuda) is a synchronous copy from pageable host memory, which a
+        # stream capture refuses (the first eager pass fills the cache; a captured pass then only reads it)
+        key = (dev, tuple(float(v) for v in model.gravity))
+        cached = getattr(model, "_gravity_dev", None)
+        if cached is None or cached[0] != key:
+            cached = (key, torch.tensor(model.gravity, **ones))
+            model._gravity_dev = cached
+        gravity = cached[1]
     coords_sum = bool(getattr(model, "_extra_flags", 0) & K.F_COORDS_SUM)         # E_GCL_vel(coords_agg='sum'), :126
     rf = bool(getattr(model, "_extra_flags", 0) & K.F_RF)   # FastRF (models/FastRF.py:155-186): no node_model / node_model_virtual,
     #                                                         the velocity head reads ||vel|| (detached, :169) instead of h

@@ -39,8 +39,11 @@ def _batch(sizes, deg, C, seed, nf=2, ea=2, loc_scale=2.0, fully_connected=False
             r, c = r[m], c[m]
         else:
             e = n * deg
-            r = torch.randint(0, n, (e,), generator=g)
-            c = torch.randint(0, n, (e,), generator=g)
+            if n == 0:   # an empty graph: no nodes, no edges (torch.randint refuses an empty range)
+                r = c = torch.zeros(0, dtype=torch.long)
+            else:
+                r = torch.randint(0, n, (e,), generator=g)
+                c = torch.randint(0, n, (e,), generator=g)
         rows.append(r + off); cols.append(c + off); batch += [b] * n; off += n
     ei = torch.stack([torch.cat(rows), torch.cat(cols)])
     ei = ei[:, torch.randperm(ei.size(1), generator=g)]
@@ -103,18 +106,18 @@ def _oracle_results(cfg, p, inp, tgt):
     return res
 
 
-def _check_vs_oracle(cfg, inp, seed, case=None, extra_flags=0, kink_tol=0.0):
-    import inspect
-    case = case or inspect.stack()[1].function
-    p, m = _models(cfg, seed)
-    m._extra_flags |= extra_flags
-    tgt = inp["node_loc"] + 0.5
-    # HIP
+def _run_module(m, inp, tgt):
+    """One eager forward + backward of the HIP module -> (loc, vloc, {parameter: gradient, zeros where .grad is None})."""
     kw = {k: v.cuda() for k, v in inp.items()}
     loc, vloc = m(**kw)
     _loss(loc, vloc, tgt.cuda()).backward()
     got = {k: (v.grad.cpu() if v.grad is not None else torch.zeros_like(v).cpu()) for k, v in m.named_parameters()}
-    # oracle fp32 and fp64
+    return loc, vloc, got
+
+
+def _compare_vs_oracle(case, cfg, p, inp, tgt, loc, vloc, got, kink_tol=0.0):
+    """The comparing half of _check_vs_oracle: outputs at 1e-5 of the fp32 oracle, the displacement and every gradient in `got` by
+    grad_check against the oracle in fp32 and fp64 (tests/test_gpu_graph_replay.py hands it the tensors a replayed graph wrote)."""
     res = _oracle_results(cfg, p, inp, tgt)
     l32, v32, g32 = res[torch.float32]
     l64, v64, g64 = res[torch.float64]
@@ -122,7 +125,7 @@ def _check_vs_oracle(cfg, inp, seed, case=None, extra_flags=0, kink_tol=0.0):
     if rel_err(loc, l32) > 1e-5: bad.append(("loc", rel_err(loc, l32)))
     if rel_err(vloc, v32) > 1e-5: bad.append(("vloc", rel_err(vloc, v32)))
     x0 = inp["node_loc"].double()
-    grad_check(case, "displacement", loc.cpu().double() - x0, l32.double() - x0, l64 - x0, bad)
+    grad_check(case, "displacement", loc.detach().cpu().double() - x0, l32.double() - x0, l64 - x0, bad)
     for k in g64:
         if kink_tol > 0.0:   # piecewise-linear activations: see test_other_activations_mid_size_vs_oracle
             if rel_err(got[k], g64[k]) > max(kink_tol, 2.0 * rel_err(g32[k], g64[k])):
@@ -130,6 +133,16 @@ def _check_vs_oracle(cfg, inp, seed, case=None, extra_flags=0, kink_tol=0.0):
         else:
             grad_check(case, k, got[k], g32[k], g64[k], bad)
     assert not bad, bad
+
+
+def _check_vs_oracle(cfg, inp, seed, case=None, extra_flags=0, kink_tol=0.0):
+    import inspect
+    case = case or inspect.stack()[1].function
+    p, m = _models(cfg, seed)
+    m._extra_flags |= extra_flags
+    tgt = inp["node_loc"] + 0.5
+    loc, vloc, got = _run_module(m, inp, tgt)
+    _compare_vs_oracle(case, cfg, p, inp, tgt, loc, vloc, got, kink_tol)
 
 
 def test_equivariance_reference_acceptance_property():
@@ -554,6 +567,24 @@ def test_no_edges_and_isolated_nodes():
     keep = inp["edge_index"][0] >= 10          # nodes 0..9 never aggregate (count clamp, :294)
     inp_iso = dict(inp, edge_index=inp["edge_index"][:, keep].contiguous(), edge_attr=inp["edge_attr"][keep].contiguous())
     _check_vs_oracle(cfg, inp_iso, seed=8)
+
+
+def _empty_middle_batch(sizes, deg, C, seed):
+    """_batch with an empty graph in the middle (data_batch skips its id); its loc_mean row, which _batch leaves zero (the mean of no
+    nodes), is set to a non-zero point: the reference divides that graph's sums by count.clamp(min=1), and a zero row would hide a
+    wrong count."""
+    inp = _batch(sizes, deg, C, seed=seed)
+    for b, n in enumerate(sizes):
+        if n == 0:
+            inp["loc_mean"][b] = torch.tensor([1.5, -0.7, 0.4]).view(3, 1) + 0.1 * torch.arange(C)
+    return inp
+
+
+def test_empty_middle_graph_vs_oracle():
+    """gptr[b] == gptr[b+1]: three graphs of 40, 0 and 25 nodes.  (The oracle takes B as batch.max() + 1, as the reference does, so only a
+    middle graph can be empty.)"""
+    cfg = R.Config(2, 0, 2, 64, 3, n_layers=2, gravity=[0, -1, 0])
+    _check_vs_oracle(cfg, _empty_middle_batch([40, 0, 25], 4, 3, seed=19), seed=19)
 
 
 def test_cfg4_full_size_properties():
