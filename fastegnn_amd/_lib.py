@@ -232,6 +232,15 @@ def lib(act: bool = False, wide=None):
     L.fastegnn_wide_act_scatter_backward.argtypes = [_vp, _vp, _i64, _i32, _i32, _f, _vp, _vp, _vp, _vp]
     L.fastegnn_wide_rowscale.argtypes = [_vp, _vp, _i64, _i32, _vp, _vp]
     L.fastegnn_wide_rowdot.argtypes = [_vp, _vp, _i64, _i32, _vp, _vp]
+    # the ordered forms of the wide path's sums (additive exports): workspace queries and the entry points that take one
+    L.fastegnn_wide_segment_sum_ws_bytes.restype = C.c_size_t
+    L.fastegnn_wide_segment_sum_ws_bytes.argtypes = [_i64, _i32]
+    L.fastegnn_wide_segment_sum_ordered.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _f, _vp, _vp, C.c_size_t, _vp]
+    L.fastegnn_wide_linear_dw_ws_bytes.restype = C.c_size_t
+    L.fastegnn_wide_linear_dw_ws_bytes.argtypes = [_i64, _i32, _i32]
+    L.fastegnn_wide_linear_dw_ordered.argtypes = [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _f, _vp, C.c_size_t, _vp]
+    L.fastegnn_wide_head_dw_ordered.argtypes = [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _f, _i32, _f, _vp,
+                                                C.c_size_t, _vp]
     L.fastegnn_sizeof_layer.restype = C.c_size_t
     L.fastegnn_sizeof_graph.restype = C.c_size_t
     if L.fastegnn_sizeof_layer() != C.sizeof(LayerT) or L.fastegnn_sizeof_graph() != C.sizeof(GraphT):
@@ -275,6 +284,8 @@ EXPORTED = STAGE_FUNCS + [
     "fastegnn_wide_linear", "fastegnn_wide_linear_dx", "fastegnn_wide_linear_dw", "fastegnn_wide_head_dx", "fastegnn_wide_head_dw", "fastegnn_wide_head_forward", "fastegnn_wide_act", "fastegnn_wide_act_backward",
     "fastegnn_wide_gather_add", "fastegnn_wide_gather2", "fastegnn_wide_scatter_add", "fastegnn_wide_scatter_add_perm", "fastegnn_wide_act_scatter",
     "fastegnn_wide_act_scatter_backward", "fastegnn_wide_rowscale", "fastegnn_wide_rowdot",
+    "fastegnn_wide_segment_sum_ws_bytes", "fastegnn_wide_segment_sum_ordered", "fastegnn_wide_linear_dw_ws_bytes",
+    "fastegnn_wide_linear_dw_ordered", "fastegnn_wide_head_dw_ordered",
 ]
 
 

@@ -4,7 +4,9 @@
 // hidden-sized tensor op as one of these launches (fastegnn_amd/wide.py assembles them, autograd composes the backward from
 // the *_dx / *_dw / *_bwd entry points).  The two GEMM kernels (wide_gemm.h) run fp32-grade products as bf16x3 splits on the
 // matrix pipe, with the activation of a Linear's input and the activation backward of its input gradient fused in; vector
-// FMAs elsewhere, fp32 atomics for the row-keyed sums.  DESIGN.md section 9 prices this path; the tuned path is hidden_nf <= 64.
+// FMAs elsewhere, fp32 atomics for the row-keyed sums -- or, for a module that asked for reproducible sums, their ORDERED forms without
+// atomics (segsum_ordered_kernel, the ORD instances of the weight-gradient kernels + ordered_reduce_kernel: DESIGN.md section 14).
+// DESIGN.md section 9 prices this path; the tuned path is hidden_nf <= 64.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -137,7 +139,9 @@ __global__ __launch_bounds__(256) void gemm_smallk_kernel(const float *A, int ld
 // gradients (S = G, L = X) and the few feature columns of a first layer (S = X, L = G); the activation applies to the side that is
 // X.  Thread = VW (4 or 1) consecutive columns l in one of the workgroup's row slots; a workgroup walks its row range with every
 // slot, the slots' partials (double: cancelling column sums over up to 10^6 rows) meet in LDS, one fp32 atomic per column and range.
-template <int NS, int VW, int PS, int PL>
+// ORD (fastegnn_wide_linear_dw_ordered): no atomic -- row range y stores its sums to slab y of a workspace (`out` = the slabs,
+// ns * nl floats each, addressed by so / sl as dW is); ordered_reduce_kernel adds the slabs in ascending y.
+template <int NS, int VW, int PS, int PL, bool ORD = false>
 __global__ __launch_bounds__(256) void tn_small_kernel(const float *S, int lds_, int ns, const float *L, int ldl, int nl, long M,
                                                        float *out, long so, long sl, long rows_per_split, int cols_per_wg, Act proS,
                                                        Act proL) {
@@ -182,20 +186,43 @@ __global__ __launch_bounds__(256) void tn_small_kernel(const float *S, int lds_,
       for (int j = 0; j < VW; ++j) {
         double t = 0.0;
         for (int q = 0; q < slots; ++q) t += red[(q * cols_per_wg + cw) * VW + j];
-        atomicAdd(out + (size_t)s * so + (size_t)(l + j) * sl, (float)t);
+        if constexpr (ORD) out[(size_t)blockIdx.y * ns * nl + (size_t)s * so + (size_t)(l + j) * sl] = (float)t;
+        else atomicAdd(out + (size_t)s * so + (size_t)(l + j) * sl, (float)t);
       }
     }
   }
 }
 
-// db[o] += sum_m G[m*ldg + o]
+// db[o] += sum_m G[m*ldg + o]        (ORD: db = the slabs of a workspace, O floats each; row range y stores to slab y)
+template <bool ORD = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const float *G, int ldg, long M, int O, float *db, long rows_per_split) {
   const long r_lo = (long)blockIdx.y * rows_per_split, r_hi = r_lo + rows_per_split < M ? r_lo + rows_per_split : M;
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= O) return;
   double s = 0.0;
   for (long m = r_lo; m < r_hi; ++m) s += (double)G[(size_t)m * ldg + o];
-  atomicAdd(db + o, (float)s);
+  if constexpr (ORD) db[(size_t)blockIdx.y * O + o] = (float)s;
+  else atomicAdd(db + o, (float)s);
+}
+// The second step of the ordered weight gradients: out[(e / inner) * ld + e % inner] += sum over s = 0 .. nsplit-1, ascending, of
+// slab[s * stride + off + e] (the sum in double, rounded once), for up to three segments of a slab (dW block, db, dw2).  One thread
+// per element: the order is the loop's.
+struct OrdSeg { long off, n; int inner; long ld; float *out; };
+struct OrdReduce { const float *slab; int nsplit; long stride; OrdSeg seg[3]; };
+__global__ __launch_bounds__(256) void ordered_reduce_kernel(OrdReduce r) {
+  const long total = r.seg[0].n + r.seg[1].n + r.seg[2].n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    long e = i;
+    int q = 0;
+    while (q < 2 && e >= r.seg[q].n) e -= r.seg[q++].n;
+    const OrdSeg g = r.seg[q];
+    const float *src = r.slab + g.off + e;
+    double t = 0.0;
+#pragma unroll 8
+    for (int s = 0; s < r.nsplit; ++s) t += (double)src[(size_t)s * r.stride];
+    float *dst = g.out + (size_t)(e / g.inner) * g.ld + e % g.inner;
+    *dst += (float)t;
+  }
 }
 
 __global__ __launch_bounds__(256) void act_kernel(const float *z, size_t n, Act a, float *y) {
@@ -343,6 +370,135 @@ __global__ __launch_bounds__(256) void scatter_add_runs_kernel(float *table, con
     }
     flush();
   }
+}
+// ---- the ORDERED segment sum (fastegnn_wide_segment_sum_ordered): scatter_add_runs_kernel without atomics ---------------------------
+// idx is SORTED (non-decreasing); rows are read through perm when given.  Slot g = rows [g * rps, (g + 1) * rps) of the sorted order,
+// rps a function of (M, W) alone (ordered_rows_per_slot).  A slot adds its rows one by one, ascending, into a sum that starts at 0.f
+// for every run.  A run that begins and ends inside one slot is stored to its table row.  A slot's FIRST run, when row g * rps - 1 has
+// the same target (the run came in from slot g - 1), goes to part[g][0]; its LAST run, when row (g + 1) * rps has the same target and
+// the run is not the one already in part[g][0], goes to part[g][1].  segsum_fold_kernel then walks every chain: part[g][1], then
+// part[g + 1][0], part[g + 2][0] .. while slot g' still starts on the chain's target, added in that order, one store.  The targets
+// of the partials are read back from idx (the index is sorted: both kernels see the same runs), so the workspace holds sums only.
+// Nothing depends on the grid, on the number of slots per workgroup or on VW.
+inline long ordered_rows_per_slot(long M, int W) {
+  long rps = 16;
+  while (rps < 256 && ((M + rps - 1) / rps) * (long)W > (1L << 21)) rps *= 2;
+  return rps;
+}
+template <int VW, int PRO>
+__global__ __launch_bounds__(256) void segsum_ordered_kernel(float *table, const int64_t *idx, const int64_t *perm, long M, int W,
+                                                             const float *rows, long rps, long n_slots, int cols_per_wg, Act pro,
+                                                             float *yout, float *part) {
+#pragma clang fp contract(off)   // the sums are plain fp32 adds of the values stored to yout: no product of the activation fused in
+  const int slots = 256 / cols_per_wg, slot = threadIdx.x / cols_per_wg, cw = threadIdx.x % cols_per_wg;
+  const int w = (blockIdx.y * cols_per_wg + cw) * VW;
+  const long g = (long)blockIdx.x * slots + slot;
+  if (w >= W || g >= n_slots) return;
+  const long m_lo = g * rps, m_hi = m_lo + rps < M ? m_lo + rps : M;
+  int64_t cur = idx[m_lo];
+  const bool first_cont = m_lo > 0 && idx[m_lo - 1] == cur;
+  const bool last_cont = m_hi < M && idx[m_hi] == idx[m_hi - 1];
+  bool first = true;
+  float acc[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) acc[j] = 0.f;
+  auto emit = [&](float *dst) {
+    if constexpr (VW == 4) *reinterpret_cast<float4 *>(dst) = float4{acc[0], acc[1], acc[2], acc[3]};
+    else *dst = acc[0];
+  };
+  for (long m = m_lo; m < m_hi; m += 4) {
+    int64_t t[4];
+    float v[4][VW];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long mm = m + u < m_hi ? m + u : m_hi - 1;
+      t[u] = idx[mm];
+      const size_t off = (size_t)(perm ? perm[mm] : mm) * W + w;
+      const float *src = rows + off;
+      if constexpr (VW == 4) {
+        const float4 q = *reinterpret_cast<const float4 *>(src);
+        v[u][0] = q.x; v[u][1] = q.y; v[u][2] = q.z; v[u][3] = q.w;
+      } else v[u][0] = *src;
+      if constexpr (PRO != AM_NONE) {
+#pragma unroll
+        for (int j = 0; j < VW; ++j) v[u][j] = pro_t<PRO>(v[u][j], pro);
+        if (m + u < m_hi) {
+          if constexpr (VW == 4) *reinterpret_cast<float4 *>(yout + off) = float4{v[u][0], v[u][1], v[u][2], v[u][3]};
+          else yout[off] = v[u][0];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (m + u >= m_hi) break;
+      if (t[u] != cur) {   // a run ends inside the slot: the slot's first run may have come in from the slot before
+        emit(first && first_cont ? part + (size_t)(2 * g) * W + w : table + (size_t)cur * W + w);
+        first = false;
+#pragma unroll
+        for (int j = 0; j < VW; ++j) acc[j] = 0.f;
+        cur = t[u];
+      }
+#pragma unroll
+      for (int j = 0; j < VW; ++j) acc[j] += v[u][j];
+    }
+  }
+  if (first && first_cont) emit(part + (size_t)(2 * g) * W + w);
+  else if (last_cont) emit(part + (size_t)(2 * g + 1) * W + w);
+  else emit(table + (size_t)cur * W + w);
+}
+// thread = (slot g, VW columns): a slot whose last run goes on into slot g + 1 and is not its own incoming run starts a chain
+template <int VW>
+__global__ __launch_bounds__(256) void segsum_fold_kernel(float *table, const int64_t *idx, long M, int W, long rps, long n_slots,
+                                                          const float *part) {
+  const int nv = W / VW;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_slots * nv) return;
+  const long g = i / nv;
+  const int w = (int)(i - g * nv) * VW;
+  const long m_lo = g * rps, m_hi = m_lo + rps;
+  if (m_hi >= M) return;                                   // the last slot: nothing goes on
+  const int64_t t = idx[m_hi - 1];
+  if (idx[m_hi] != t) return;                              // the last run ends with the slot
+  if (idx[m_lo] == t && m_lo > 0 && idx[m_lo - 1] == t) return;   // one run through the whole slot that came in: part[g][0], another chain's
+  float acc[VW];
+  auto add = [&](const float *src, bool init) {
+    if constexpr (VW == 4) {
+      const float4 q = *reinterpret_cast<const float4 *>(src);
+      if (init) { acc[0] = q.x; acc[1] = q.y; acc[2] = q.z; acc[3] = q.w; }
+      else { acc[0] += q.x; acc[1] += q.y; acc[2] += q.z; acc[3] += q.w; }
+    } else {
+      if (init) acc[0] = *src;
+      else acc[0] += *src;
+    }
+  };
+  // the chain goes on through every slot that starts on t: slots g + 1 .. g_end - 1 (the index is sorted: a binary search), so that
+  // the loads of eight partials are in flight together -- the adds keep their order
+  long g_end = g + 1, hi = n_slots;
+  while (g_end < hi) {
+    const long mid = (g_end + hi) >> 1;
+    if (idx[mid * rps] == t) g_end = mid + 1;
+    else hi = mid;
+  }
+  add(part + (size_t)(2 * g + 1) * W + w, true);
+  long g2 = g + 1;
+  for (; g2 + 8 <= g_end; g2 += 8) {
+    float q[8][VW];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const float *src = part + (size_t)(2 * (g2 + u)) * W + w;
+      if constexpr (VW == 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(src);
+        q[u][0] = v.x; q[u][1] = v.y; q[u][2] = v.z; q[u][3] = v.w;
+      } else q[u][0] = *src;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int j = 0; j < VW; ++j) acc[j] += q[u][j];
+  }
+  for (; g2 < g_end; ++g2) add(part + (size_t)(2 * g2) * W + w, false);
+  if constexpr (VW == 4) *reinterpret_cast<float4 *>(table + (size_t)t * W + w) = float4{acc[0], acc[1], acc[2], acc[3]};
+  else table[(size_t)t * W + w] = acc[0];
 }
 // Y[m, :] = X[m, :] * s[m]
 __global__ __launch_bounds__(256) void rowscale_kernel(const float *X, const float *s, long M, int W, float *Y) {
@@ -529,7 +685,7 @@ static int linear_dw(const float *G, const float *X, int64_t M, int32_t O, int32
   }
   if (db) {
     const int gx = cdiv(O, 256), ns = row_splits(M, gx);
-    hipLaunchKernelGGL(colsum_kernel, dim3(gx, ns), dim3(256), 0, st, G, O, (long)M, O, db, (long)cdiv(M, ns));
+    hipLaunchKernelGGL(colsum_kernel<false>, dim3(gx, ns), dim3(256), 0, st, G, O, (long)M, O, db, (long)cdiv(M, ns));
     return check_launch("fastegnn_wide_linear_dw(bias)");
   }
   return FASTEGNN_OK;
@@ -537,6 +693,128 @@ static int linear_dw(const float *G, const float *X, int64_t M, int32_t O, int32
 int fastegnn_wide_linear_dw(const float *G, const float *X, int64_t M, int32_t O, int32_t K, float *dW, int32_t ldw, int32_t c0,
                             float *db, int32_t act_kind, float act_p, void *stream) {
   return linear_dw(G, X, M, O, K, dW, ldw, c0, db, act_kind, act_p, stream, nullptr, nullptr, Act{ACT_NONE, 0.f});
+}
+// ---- the ORDERED weight gradients: every row split stores its partial sums to a slab of the caller's workspace (the kernels' ORD
+// forms), ordered_reduce_kernel adds the slabs in ascending split order, in double, and adds the total into dW / db / dw2 once.
+// The split plan is a function of (M, O, K) alone.
+struct OrdPlan { bool small; long rows; int nz; size_t floats; };
+static OrdPlan ordered_dw_plan(long M, int O, int K) {
+  OrdPlan p{O <= 8 || K <= 8, 0, 0, 0};
+  if (M <= 0) return p;
+  if (p.small) {   // the two small-side forms: ranges of at least 512 rows, at most 512 of them and 4 MiB of slabs (O * K floats each, then the bias slabs)
+    long ns = (M + 511) / 512;
+    const long cap = (4L << 20) / (4L * ((long)O * K + O));
+    ns = ns > 512 ? 512 : ns;
+    ns = ns > cap ? cap : ns;
+    ns = ns < 1 ? 1 : ns;
+    p.rows = (M + ns - 1) / ns;
+    p.nz = (int)((M + p.rows - 1) / p.rows);
+    p.floats = (size_t)p.nz * ((size_t)O * K + O);
+  } else {         // the 128 x 128 block kernel: about 512 workgroups, ranges of at least 256 rows, at most 16 MiB of slabs
+    const long blocks = (long)cdiv(O, TB) * cdiv(K, TB), per = (long)O * K + 2L * O;
+    long ns = (512 + blocks - 1) / blocks;
+    const long most = (M + 255) / 256, cap = (16L << 20) / (per * 4);
+    if (ns > most) ns = most;
+    if (ns > cap) ns = cap;
+    if (ns < 1) ns = 1;
+    p.rows = ((M + ns - 1) / ns + 31) / 32 * 32;
+    p.nz = (int)((M + p.rows - 1) / p.rows);
+    p.floats = (size_t)p.nz * per;
+  }
+  return p;
+}
+static int linear_dw_ordered(const float *G, const float *X, int64_t M, int32_t O, int32_t K, float *dW, int32_t ldw, int32_t c0, float *db,
+                             int32_t act_kind, float act_p, float *ws, size_t ws_bytes, void *stream, const float *gs, const float *w2,
+                             Act gen, float *dw2 = nullptr) {
+  FE_REQUIRE(M >= 0 && K >= 1 && O >= 1 && ldw >= c0 + K && c0 >= 0 && act_ok(act_kind), "fastegnn_wide_linear_dw_ordered: bad arguments");
+  FE_REQUIRE((G && X) || M == 0, "fastegnn_wide_linear_dw_ordered: null pointer");
+  FE_REQUIRE(!gs || (dW && O > 8 && K > 8), "fastegnn_wide_head_dw_ordered: widths of at least 9");
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0 || (!dW && !db && !dw2)) return FASTEGNN_OK;
+  const OrdPlan pl = ordered_dw_plan(M, O, K);
+  FE_REQUIRE(ws && ws_bytes >= pl.floats * sizeof(float) && (reinterpret_cast<size_t>(ws) & 15) == 0,
+             "fastegnn_wide_linear_dw_ordered: workspace smaller than fastegnn_wide_linear_dw_ws_bytes (or not 16-byte aligned)");
+  const Act pro{act_kind, act_p};
+  const OrdSeg none{0, 0, 1, 0, nullptr};
+  if (!pl.small) {
+    const long per = (long)O * K + 2L * O;
+    if (dW) {
+      TnX3 t{G, O, X, K, (long)M, O, K, ws, K, 0, pl.rows, db ? ws + (size_t)O * K : nullptr, pro, gs, w2, gen,
+             dw2 ? ws + (size_t)O * K + O : nullptr};
+      const dim3 grid(cdiv(O, TB), cdiv(K, TB), (unsigned)pl.nz);
+      launch_tn_x3_ordered(t, am_of(act_kind), gs ? am_of(gen.kind) : AM_NONE, grid, st);
+      int rc = check_launch("fastegnn_wide_linear_dw_ordered");
+      if (rc) return rc;
+      OrdReduce r{ws, pl.nz, per, {OrdSeg{0, (long)O * K, K, ldw, dW + c0}, db ? OrdSeg{(long)O * K, O, O, 0, db} : none,
+                                   dw2 ? OrdSeg{(long)O * K + O, O, O, 0, dw2} : none}};
+      hipLaunchKernelGGL(ordered_reduce_kernel, dim3(grid1d((size_t)per)), dim3(256), 0, st, r);
+      return check_launch("fastegnn_wide_linear_dw_ordered(reduce)");
+    }
+  } else if (dW) {
+    const bool g_small = O <= 8;
+    const float *S = g_small ? G : X, *Lg = g_small ? X : G;
+    const int nsm = g_small ? O : K, nl = g_small ? K : O;
+    const long so = g_small ? K : 1, sl = g_small ? 1 : K;   // the slab is the [O, K] block itself
+    const int vw = ((nl & 3) == 0 && (reinterpret_cast<size_t>(Lg) & 15) == 0) ? 4 : 1;
+    // the rows of a range go to 256 / cols slots whose sums meet in a fixed order: cols from the width alone, so that the order
+    // does not depend on the operand's alignment (vw = 1 on a width that is a multiple of 4 runs four times the workgroups)
+    const int cols4 = (nl & 3) == 0 ? nl / 4 : nl, cols = cols4 >= 256 ? 256 : pow2_at_least(cols4);
+    const dim3 grid(cdiv(nl / vw, cols), pl.nz);
+    const int am = am_of(act_kind), ps = g_small ? AM_NONE : am, pl_ = g_small ? am : AM_NONE;
+#define FE_TNS(NS_, VW_, PS_, PL_)                                                                                                   \
+  hipLaunchKernelGGL((tn_small_kernel<NS_, VW_, PS_, PL_, true>), grid, dim3(256), 0, st, S, nsm, nsm, Lg, nl, nl, (long)M, ws, so, sl, \
+                     pl.rows, cols, pro, pro)
+#define FE_TNS_ACT(NS_, VW_)                                           \
+  do {                                                                 \
+    if (ps == AM_SILU) FE_TNS(NS_, VW_, AM_SILU, AM_NONE);             \
+    else if (ps == AM_GEN) FE_TNS(NS_, VW_, AM_GEN, AM_NONE);          \
+    else if (pl_ == AM_SILU) FE_TNS(NS_, VW_, AM_NONE, AM_SILU);       \
+    else if (pl_ == AM_GEN) FE_TNS(NS_, VW_, AM_NONE, AM_GEN);         \
+    else FE_TNS(NS_, VW_, AM_NONE, AM_NONE);                           \
+  } while (0)
+    if (vw == 4) {
+      if (nsm == 1) FE_TNS_ACT(1, 4);
+      else if (nsm <= 4) FE_TNS_ACT(4, 4);
+      else FE_TNS_ACT(8, 4);
+    } else {
+      if (nsm == 1) FE_TNS_ACT(1, 1);
+      else FE_TNS_ACT(8, 1);
+    }
+#undef FE_TNS_ACT
+#undef FE_TNS
+    int rc = check_launch("fastegnn_wide_linear_dw_ordered");
+    if (rc) return rc;
+    OrdReduce r{ws, pl.nz, (long)O * K, {OrdSeg{0, (long)O * K, K, ldw, dW + c0}, none, none}};
+    hipLaunchKernelGGL(ordered_reduce_kernel, dim3(grid1d((size_t)O * K)), dim3(256), 0, st, r);
+    rc = check_launch("fastegnn_wide_linear_dw_ordered(reduce)");
+    if (rc) return rc;
+  }
+  if (db) {   // (the block kernel without dW, and the small forms: the column sums over the same kind of row ranges)
+    const long rows = pl.small ? pl.rows : (M + pl.nz - 1) / pl.nz;
+    const int nz = (int)((M + rows - 1) / rows);
+    float *bslab = ws + (pl.small ? (size_t)pl.nz * O * K : 0);
+    hipLaunchKernelGGL(colsum_kernel<true>, dim3(cdiv(O, 256), nz), dim3(256), 0, st, G, O, (long)M, O, bslab, rows);
+    int rc = check_launch("fastegnn_wide_linear_dw_ordered(bias)");
+    if (rc) return rc;
+    OrdReduce r{bslab, nz, (long)O, {OrdSeg{0, O, O, 0, db}, none, none}};
+    hipLaunchKernelGGL(ordered_reduce_kernel, dim3(grid1d((size_t)O)), dim3(256), 0, st, r);
+    return check_launch("fastegnn_wide_linear_dw_ordered(bias reduce)");
+  }
+  return FASTEGNN_OK;
+}
+size_t fastegnn_wide_linear_dw_ws_bytes(int64_t M, int32_t O, int32_t K) {
+  if (M <= 0 || O < 1 || K < 1) return 0;
+  return ordered_dw_plan(M, O, K).floats * sizeof(float);
+}
+int fastegnn_wide_linear_dw_ordered(const float *G, const float *X, int64_t M, int32_t O, int32_t K, float *dW, int32_t ldw, int32_t c0,
+                                    float *db, int32_t act_kind, float act_p, float *ws, size_t ws_bytes, void *stream) {
+  return linear_dw_ordered(G, X, M, O, K, dW, ldw, c0, db, act_kind, act_p, ws, ws_bytes, stream, nullptr, nullptr, Act{ACT_NONE, 0.f});
+}
+int fastegnn_wide_head_dw_ordered(const float *gs, const float *w2, const float *Zc, const float *X, int64_t M, int32_t O, int32_t K,
+                                  float *dW, int32_t ldw, int32_t c0, float *db, float *dw2, int32_t kind, float p, int32_t x_kind,
+                                  float x_p, float *ws, size_t ws_bytes, void *stream) {
+  FE_REQUIRE(kind >= 0 && kind <= FASTEGNN_ACT_SOFTPLUS && (M == 0 || (gs && w2)), "fastegnn_wide_head_dw_ordered: bad arguments");
+  return linear_dw_ordered(Zc, X, M, O, K, dW, ldw, c0, db, x_kind, x_p, ws, ws_bytes, stream, gs, w2, Act{kind, p}, dw2);
 }
 // The backward of the FIRST Linear of a scalar head  s = act(X W1^T + b1) . w2^T (+ b2)  (coord_mlp_r / _r_virtual / _v_virtual / _vel,
 // gravity_mlp: models/FastEGNN.py:55-99) straight from the head's output gradient gs [M]: the gradient of the hidden
@@ -701,6 +979,46 @@ int fastegnn_wide_scatter_add_perm(float *table, const int64_t *idx_sorted, cons
   if (M == 0) return FASTEGNN_OK;
   FE_REQUIRE(table && idx_sorted && perm && rows, "fastegnn_wide_scatter_add_perm: null pointer");
   return scatter_add(table, idx_sorted, perm, M, W, rows, (hipStream_t)stream, "fastegnn_wide_scatter_add_perm");
+}
+// ---- the ordered segment sum (kernels: segsum_ordered_kernel + segsum_fold_kernel above) ----
+size_t fastegnn_wide_segment_sum_ws_bytes(int64_t M, int32_t W) {
+  if (M <= 0 || W < 1) return 0;
+  const long rps = ordered_rows_per_slot(M, W);
+  return (size_t)((M + rps - 1) / rps) * 2 * (size_t)W * sizeof(float);
+}
+int fastegnn_wide_segment_sum_ordered(float *table, const int64_t *idx_sorted, const int64_t *perm, int64_t M, int32_t W, const float *rows,
+                                      int32_t act_kind, float act_p, float *y, float *ws, size_t ws_bytes, void *stream) {
+  FE_REQUIRE(M >= 0 && W >= 1 && act_ok(act_kind) && (act_kind < 0) == (y == nullptr), "fastegnn_wide_segment_sum_ordered: bad arguments");
+  if (M == 0) return FASTEGNN_OK;
+  FE_REQUIRE(table && idx_sorted && rows, "fastegnn_wide_segment_sum_ordered: null pointer");
+  FE_REQUIRE(ws && ws_bytes >= fastegnn_wide_segment_sum_ws_bytes(M, W) && (reinterpret_cast<size_t>(ws) & 15) == 0,
+             "fastegnn_wide_segment_sum_ordered: workspace smaller than fastegnn_wide_segment_sum_ws_bytes (or not 16-byte aligned)");
+  hipStream_t st = (hipStream_t)stream;
+  const Act pro{act_kind, act_p};
+  const bool v4 = (W & 3) == 0 && ((reinterpret_cast<size_t>(rows) | reinterpret_cast<size_t>(table) | reinterpret_cast<size_t>(y)) & 15) == 0;
+  const int nv = v4 ? W / 4 : W, pm = y ? am_of(act_kind) : AM_NONE;
+  const int cols = nv >= 256 ? 256 : pow2_at_least(nv), slots = 256 / cols, gy = cdiv(nv, cols);
+  const long rps = ordered_rows_per_slot(M, W), n_slots = (M + rps - 1) / rps, gx = (n_slots + slots - 1) / slots;
+  FE_REQUIRE(gx <= 0x7fffffffL && gy <= 65535 && (n_slots * nv + 255) / 256 <= 0x7fffffffL, "fastegnn_wide_segment_sum_ordered: too many rows or columns");
+#define FE_SO(VW_, P_)                                                                                                                   \
+  hipLaunchKernelGGL((segsum_ordered_kernel<VW_, P_>), dim3((unsigned)gx, gy), dim3(256), 0, st, table, idx_sorted, perm, (long)M, W, rows, rps, \
+                     n_slots, cols, pro, y, ws)
+  if (v4) {
+    if (pm == AM_SILU) FE_SO(4, AM_SILU);
+    else if (pm == AM_GEN) FE_SO(4, AM_GEN);
+    else FE_SO(4, AM_NONE);
+  } else {
+    if (pm == AM_SILU) FE_SO(1, AM_SILU);
+    else if (pm == AM_GEN) FE_SO(1, AM_GEN);
+    else FE_SO(1, AM_NONE);
+  }
+#undef FE_SO
+  int rc = check_launch("fastegnn_wide_segment_sum_ordered");
+  if (rc || n_slots < 2) return rc;
+  const unsigned fg = (unsigned)((n_slots * nv + 255) / 256);
+  if (v4) hipLaunchKernelGGL(segsum_fold_kernel<4>, dim3(fg), dim3(256), 0, st, table, idx_sorted, (long)M, W, rps, n_slots, ws);
+  else hipLaunchKernelGGL(segsum_fold_kernel<1>, dim3(fg), dim3(256), 0, st, table, idx_sorted, (long)M, W, rps, n_slots, ws);
+  return check_launch("fastegnn_wide_segment_sum_ordered(fold)");
 }
 // Y[m, :] = X[m, :] * s[m]                                (attention gates, 1 / count of the segment means)
 int fastegnn_wide_rowscale(const float *X, const float *s, int64_t M, int32_t W, float *Y, void *stream) {

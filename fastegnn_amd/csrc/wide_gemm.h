@@ -425,7 +425,10 @@ struct TnX3 {
 };
 
 #ifdef FE_WIDE_GEMM_IMPL
-template <int PRO, int GEN>
+// ORD (the ordered form, fastegnn_wide_linear_dw_ordered): no atomics -- row split z stores its block, its column sums and its dw2
+// sums to slab z of a workspace (t.dW = the slabs, [O, Kd] blocks of stride O * Kd + 2 O; t.db / t.dw2 = the two [O] tails of slab 0)
+// and ordered_reduce_kernel (wide.hip) adds the slabs in ascending z
+template <int PRO, int GEN, bool ORD = false>
 __global__ __launch_bounds__(256) void tn_x3_kernel(TnX3 t) {
   __shared__ __attribute__((aligned(16))) char sm[TN_LDS];
   __shared__ double bred[8][128];
@@ -550,6 +553,7 @@ __global__ __launch_bounds__(256) void tn_x3_kernel(TnX3 t) {
   }
   // acc[i][j][r]: output o0 + wo + 32 i + 8 (r / 4) + 4 hh + r % 4, input k0 + wk + 32 j + l32
   const int l32 = lane & 31, hh = lane >> 5;
+  const size_t slab = ORD ? (size_t)blockIdx.z * ((size_t)t.O * t.Kd + 2 * (size_t)t.O) : 0;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -559,7 +563,11 @@ __global__ __launch_bounds__(256) void tn_x3_kernel(TnX3 t) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int o = o0 + wo + 32 * i + 8 * (r >> 2) + 4 * hh + (r & 3);
-        if (o < t.O) atomicAdd(t.dW + (size_t)o * t.ldw + t.c0 + k, acc[i][j][r]);
+        if constexpr (ORD) {
+          if (o < t.O) t.dW[slab + (size_t)o * t.Kd + k] = acc[i][j][r];
+        } else {
+          if (o < t.O) atomicAdd(t.dW + (size_t)o * t.ldw + t.c0 + k, acc[i][j][r]);
+        }
       }
     }
   if (do_bias) {   // column 4 sc + e summed over the 8 staging rows' threads
@@ -570,7 +578,8 @@ __global__ __launch_bounds__(256) void tn_x3_kernel(TnX3 t) {
       double s = 0.0;
 #pragma unroll
       for (int r = 0; r < 8; ++r) s += bred[r][tid];
-      atomicAdd(t.db + o0 + tid, (float)s);
+      if constexpr (ORD) t.db[slab + o0 + tid] = (float)s;
+      else atomicAdd(t.db + o0 + tid, (float)s);
     }
   }
   if (do_w2) {
@@ -582,7 +591,8 @@ __global__ __launch_bounds__(256) void tn_x3_kernel(TnX3 t) {
       double s = 0.0;
 #pragma unroll
       for (int r = 0; r < 8; ++r) s += bred[r][tid];
-      atomicAdd(t.dw2 + o0 + tid, (float)s);
+      if constexpr (ORD) t.dw2[slab + o0 + tid] = (float)s;
+      else atomicAdd(t.dw2 + o0 + tid, (float)s);
     }
   }
 }
@@ -592,6 +602,7 @@ __global__ __launch_bounds__(256) void tn_x3_kernel(TnX3 t) {
 // host side of the two kernels (wide_gemm.hip -- its own translation unit: 25 instances, two minutes of compile time)
 int launch_gemm_x3(const GemmX3 &g, int nq, int pro_mode, int epi_mode, bool deep, dim3 grid, hipStream_t st);
 int launch_tn_x3(const TnX3 &t, int pro_mode, int gen_mode, dim3 grid, hipStream_t st);
+int launch_tn_x3_ordered(const TnX3 &t, int pro_mode, int gen_mode, dim3 grid, hipStream_t st);   // the ORD instances (part 6)
 
 }  // namespace wide
 }  // namespace fe

@@ -1,6 +1,6 @@
 // Host side of the wide path's two GEMM kernels (wide_gemm.h): one instance per (column quadrants, fused activation mode, prefetch
 // depth).  The instances take six minutes to compile and depend on none of the build variants' switches, so this file is compiled
-// ONCE per part (-DFE_WG_PART=0..5: the Makefile's wide_gemm_p*.o, in parallel) and linked into every library.
+// ONCE per part (-DFE_WG_PART=0..6: the Makefile's wide_gemm_p*.o, in parallel) and linked into every library.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #ifndef FE_ACT_GENERIC
@@ -10,7 +10,7 @@
 #include "wide_gemm.h"
 
 #ifndef FE_WG_PART
-#error "compile with -DFE_WG_PART=0..5"
+#error "compile with -DFE_WG_PART=0..6"
 #endif
 
 namespace fe {
@@ -63,6 +63,27 @@ void launch_gemm_x3_deep_head(const GemmX3 &g, int pm, int em, dim3 grid, hipStr
   else if (pm == AM_HEAD_GEN) FE_X3_ONE(4, AM_HEAD_GEN, AM_NONE, true);
   else if (em == AM_DOT_SILU) FE_X3_ONE(4, AM_NONE, AM_DOT_SILU, true);
   else FE_X3_ONE(4, AM_NONE, AM_DOT_GEN, true);
+}
+#elif FE_WG_PART == 6
+// the ordered weight gradient: the same eight (prologue, generated-gradient) forms with ORD = true
+int launch_tn_x3_ordered(const TnX3 &t, int pm, int gm, dim3 grid, hipStream_t st) {
+  if (gm == AM_SILU) {
+    if (pm == AM_SILU) hipLaunchKernelGGL((tn_x3_kernel<AM_SILU, AM_SILU, true>), grid, dim3(256), 0, st, t);
+    else if (pm == AM_GEN) hipLaunchKernelGGL((tn_x3_kernel<AM_GEN, AM_SILU, true>), grid, dim3(256), 0, st, t);
+    else hipLaunchKernelGGL((tn_x3_kernel<AM_NONE, AM_SILU, true>), grid, dim3(256), 0, st, t);
+    return 0;
+  }
+  if (gm == AM_GEN) {
+    if (pm != AM_NONE) hipLaunchKernelGGL((tn_x3_kernel<AM_GEN, AM_GEN, true>), grid, dim3(256), 0, st, t);
+    else hipLaunchKernelGGL((tn_x3_kernel<AM_NONE, AM_GEN, true>), grid, dim3(256), 0, st, t);
+    return 0;
+  }
+  switch (pm) {
+    case AM_SILU: hipLaunchKernelGGL((tn_x3_kernel<AM_SILU, AM_NONE, true>), grid, dim3(256), 0, st, t); break;
+    case AM_GEN: hipLaunchKernelGGL((tn_x3_kernel<AM_GEN, AM_NONE, true>), grid, dim3(256), 0, st, t); break;
+    default: hipLaunchKernelGGL((tn_x3_kernel<AM_NONE, AM_NONE, true>), grid, dim3(256), 0, st, t); break;
+  }
+  return 0;
 }
 #else
 void launch_gemm_x3_nq12(const GemmX3 &g, int nq, int pm, int em, dim3 grid, hipStream_t st);

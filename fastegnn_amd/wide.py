@@ -17,6 +17,9 @@ node_model_virtual) on the operators of ``csrc/wide.hip`` + ``csrc/wide_gemm.h``
 
 The edges are put in row order once per forward and the column sums go through a sorting permutation, so every edge-sized sum is a
 sum over runs.  What stays in torch is the elementwise 3-vector geometry (``[E,3]``, ``[N,3,C]``, ``[B,C,C]`` tensors) and views.
+``deterministic = True`` (``FASTEGNN_DETERMINISTIC=1``) routes every sum -- segment sums, weight, bias and head gradients -- to the
+ORDERED operators (``fastegnn_wide_segment_sum_ordered``, ``_linear_dw_ordered``, ``_head_dw_ordered``: no floating-point atomics, an
+order fixed by shapes and index contents): two runs on the same inputs agree bit for bit.
 ``FASTEGNN_WIDE_FUSE=0`` runs every activation, head and segment sum as its own launch (A/B lever).  DESIGN.md section 9 prices the
 path.  No CPU fallback: the library is loaded on first use and its absence raises."""
 from __future__ import annotations
@@ -41,6 +44,11 @@ class HipOps:
         K.check(getattr(K.lib(), "fastegnn_wide_" + name)(*[K.ptr(a) if torch.is_tensor(a) or a is None else a for a in args],
                                                           _stream(dev)), "fastegnn_wide_" + name)
 
+    @staticmethod
+    def query(name, *args):
+        """a workspace size in bytes (the size_t fastegnn_wide_*_ws_bytes queries: host only)"""
+        return int(getattr(K.lib(), "fastegnn_wide_" + name)(*args))
+
 
 _OPS = HipOps
 
@@ -51,6 +59,60 @@ def _call(name, *args):
 
 def _f32(t):
     return t.contiguous().float()
+
+
+class _Ordered:
+    """The ordered mode of one module (`deterministic = True`): every sum of the path goes to the operators that add in a fixed order
+    without atomics.  Holds their workspace -- one buffer per device, grown on demand, never released while the module lives (a
+    buffer that was outgrown is still read by kernels already queued: the stream-ordered allocator keeps it until they are done)."""
+
+    def __init__(self):
+        self._buf = {}
+
+    def ws(self, dev, nbytes):
+        b = self._buf.get(dev)
+        if b is None or b.numel() < nbytes:
+            b = torch.empty(max(-(-nbytes // (1 << 20)) << 20, 1 << 20), dtype=torch.uint8, device=dev)
+            self._buf[dev] = b
+        return b
+
+    def ws_bytes(self):
+        return sum(b.numel() for b in self._buf.values())
+
+
+_DET = None   # the _Ordered of the forward being built (every autograd node keeps it for its backward); None: the atomic operators
+
+
+def _ordered_of(model):
+    """the module's _Ordered when reproducible sums were asked for, else None.  FastEGNN / FastRF keep the request in `_deterministic`
+    (None: not asked), EGNN in a plain `deterministic` attribute; both follow FASTEGNN_DETERMINISTIC"""
+    asked = model._deterministic if hasattr(model, "_deterministic") else getattr(model, "deterministic", False)
+    if asked is not True:
+        return None
+    det = getattr(model, "_wide_ordered", None)
+    if det is None:
+        det = model._wide_ordered = _Ordered()
+    return det
+
+
+def _osum(det, table, idx, rows, order=None, act=None, y=None):
+    """the ordered segment sum: table[t] = sum of (act of) the rows with target t, in the order of the stably sorted index.
+    `order` = (idx_sorted, perm) of an index in no particular order; None: idx is sorted as it is"""
+    M, W = idx.numel(), rows.size(1)
+    srt, perm = order if order is not None else (idx, None)
+    nb = _OPS.query("segment_sum_ws_bytes", M, W)
+    kind, p = act if act is not None else (K.ACT_NONE, 0.0)
+    _call("segment_sum_ordered", table, srt, perm, M, W, rows, kind, p, y, det.ws(rows.device, nb), nb)
+
+
+def _dw(det, name, M, O, Kc, *args):
+    """linear_dw / head_dw: the atomic form, or with `det` the ordered form on its workspace"""
+    if det is None:
+        _call(name, *args)
+    else:
+        nb = _OPS.query("linear_dw_ws_bytes", M, O, Kc)
+        dev = next(a.device for a in args if torch.is_tensor(a))
+        _call(name + "_ordered", *args, det.ws(dev, nb), nb)
 
 
 class _Linear(torch.autograd.Function):
@@ -68,6 +130,7 @@ class _Linear(torch.autograd.Function):
         _call("linear", X, M, Kc, W, W.size(1), c0, b, bs, out, O, kind, p)
         ctx.save_for_backward(X, W)
         ctx.meta = (c0, Kc, bias is not None, base is not None, act)
+        ctx.det = _DET
         return out
 
     @staticmethod
@@ -85,7 +148,7 @@ class _Linear(torch.autograd.Function):
         if want_w or want_b:
             gW = torch.zeros_like(W) if want_w else None
             gb = torch.zeros(O, dtype=torch.float32, device=g.device) if want_b else None
-            _call("linear_dw", g, X, M, O, Kc, gW, W.size(1), c0, gb, kind, p)
+            _dw(ctx.det, "linear_dw", M, O, Kc, g, X, M, O, Kc, gW, W.size(1), c0, gb, kind, p)
         return gX, gW, None, None, gb, (g if has_base else None), None
 
 
@@ -104,6 +167,7 @@ class _Head(torch.autograd.Function):
               K.ACT_NONE, 0.0)
         ctx.save_for_backward(X, W1, w2, zc)
         ctx.meta = (act, b2 is not None)
+        ctx.det = _DET
         return s
 
     @staticmethod
@@ -121,7 +185,7 @@ class _Head(torch.autograd.Function):
             _call("head_dx", gs, w2, zc, M, O, W1, W1.size(1), 0, Kx, gX, 0, kind, p)
         gW1 = torch.zeros_like(W1)
         gb1 = torch.zeros(O, dtype=torch.float32, device=dev)
-        _call("head_dw", gs, w2, zc, X, M, O, Kx, gW1, W1.size(1), 0, gb1, gw2, kind, p, K.ACT_NONE, 0.0)   # (gw2 from the same pass)
+        _dw(ctx.det, "head_dw", M, O, Kx, gs, w2, zc, X, M, O, Kx, gW1, W1.size(1), 0, gb1, gw2, kind, p, K.ACT_NONE, 0.0)   # (gw2 from the same pass)
         return gX, gW1, gb1, gw2, gb2, None
 
 
@@ -145,6 +209,7 @@ class _Head2(torch.autograd.Function):
             saved += [W1, w2, zc]
         ctx.save_for_backward(*saved)
         ctx.act = act
+        ctx.det = _DET
         return tuple(outs)
 
     @staticmethod
@@ -164,7 +229,7 @@ class _Head2(torch.autograd.Function):
                 _call("head_dx", gs, w2, zc, M, O, W1, W1.size(1), 0, Kx, gX, i, kind, p)
             gW1 = torch.zeros_like(W1)
             gb1 = torch.zeros(O, dtype=torch.float32, device=dev)
-            _call("head_dw", gs, w2, zc, X, M, O, Kx, gW1, W1.size(1), 0, gb1, gw2, kind, p, K.ACT_NONE, 0.0)
+            _dw(ctx.det, "head_dw", M, O, Kx, gs, w2, zc, X, M, O, Kx, gW1, W1.size(1), 0, gb1, gw2, kind, p, K.ACT_NONE, 0.0)
             res += [gW1, gb1, gw2]
         return (gX, *res, None)
 
@@ -202,33 +267,39 @@ class _Act(torch.autograd.Function):
 
 
 class _GatherAdd(torch.autograd.Function):
-    """out[m] = (base[m]) + X[idx[m]]"""
+    """out[m] = (base[m]) + X[idx[m]]; `order` = (idx sorted, its permutation) of an unsorted idx: what the ordered mode's backward sums by"""
 
     @staticmethod
-    def forward(ctx, X, idx, base):
+    def forward(ctx, X, idx, base, order=None):
         X = _f32(X)
         M, W = idx.numel(), X.size(1)
         out = torch.empty(M, W, dtype=torch.float32, device=X.device)
         bs = _f32(base) if base is not None else None
         _call("gather_add", X, idx, M, W, bs, out)
-        ctx.save_for_backward(idx)
+        ctx.det = _DET
+        ctx.save_for_backward(idx, *(order if ctx.det is not None and order is not None else ()))
         ctx.meta = (X.size(0), base is not None)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        (idx,) = ctx.saved_tensors
+        idx = ctx.saved_tensors[0]
         g = _f32(g)
         gX = None
         if ctx.needs_input_grad[0]:
             gX = torch.zeros(ctx.meta[0], g.size(1), dtype=torch.float32, device=g.device)
-            _call("scatter_add", gX, idx, idx.numel(), g.size(1), g)
-        return gX, None, (g if ctx.meta[1] else None)
+            if ctx.det is not None:
+                _osum(ctx.det, gX, idx, g, tuple(ctx.saved_tensors[1:3]) or None)
+            else:
+                _call("scatter_add", gX, idx, idx.numel(), g.size(1), g)
+        return gX, None, (g if ctx.meta[1] else None), None
 
 
-def _scatter(table, idx, rows, order=None):
+def _scatter(table, idx, rows, order=None, det=None):
     """table[idx[m]] += rows[m]; `order` = (idx_sorted, perm) of an index in no particular order: its sums as sorted runs"""
-    if order is not None and rows.size(1) >= 32:
+    if det is not None:
+        _osum(det, table, idx, rows, order)
+    elif order is not None and rows.size(1) >= 32:
         _call("scatter_add_perm", table, order[0], order[1], idx.numel(), rows.size(1), rows)
     else:
         _call("scatter_add", table, idx, idx.numel(), rows.size(1), rows)
@@ -251,6 +322,7 @@ class _Gather2(torch.autograd.Function):
         _call("gather2", P, i1, Q, i2, feat, nf, W, W.size(1), c0, None, out, M, Wd)
         ctx.save_for_backward(i1, i2, feat, W, *(order2 if order2 is not None else ()))
         ctx.meta = (P.size(0), Q.size(0) if Q is not None else 0, c0, nf, order2 is not None)
+        ctx.det = _DET
         return out
 
     @staticmethod
@@ -263,17 +335,17 @@ class _Gather2(torch.autograd.Function):
         gP = gQ = gfeat = gW = None
         if ctx.needs_input_grad[0]:
             gP = torch.zeros(nP, Wd, dtype=torch.float32, device=g.device)
-            _scatter(gP, i1, g)
+            _scatter(gP, i1, g, None, ctx.det)
         if i2 is not None and ctx.needs_input_grad[2]:
             gQ = torch.zeros(nQ, Wd, dtype=torch.float32, device=g.device)
-            _scatter(gQ, i2, g, order2)
+            _scatter(gQ, i2, g, order2, ctx.det)
         if feat is not None:
             if ctx.needs_input_grad[4]:
                 gfeat = torch.empty(M, nf, dtype=torch.float32, device=g.device)
                 _call("linear_dx", g, M, Wd, W, W.size(1), c0, nf, gfeat, 0, None, K.ACT_NONE, 0.0)
             if ctx.needs_input_grad[5]:
                 gW = torch.zeros_like(W)
-                _call("linear_dw", g, feat, M, Wd, nf, gW, W.size(1), c0, None, K.ACT_NONE, 0.0)
+                _dw(ctx.det, "linear_dw", M, Wd, nf, g, feat, M, Wd, nf, gW, W.size(1), c0, None, K.ACT_NONE, 0.0)
         return gP, None, gQ, None, gfeat, gW, None, None
 
 
@@ -282,11 +354,14 @@ class _ActScatter(torch.autograd.Function):
     dz = (g_y + g_table[idx]) * act'(z)."""
 
     @staticmethod
-    def forward(ctx, z, idx, R, act):
+    def forward(ctx, z, idx, R, act, order=None):
         z = _f32(z)
         y = torch.empty_like(z)
         table = torch.zeros(R, z.size(1), dtype=torch.float32, device=z.device)
-        _call("act_scatter", z, idx, idx.numel(), z.size(1), act[0], act[1], y, table)
+        if _DET is not None:
+            _osum(_DET, table, idx, z, order, act, y)
+        else:
+            _call("act_scatter", z, idx, idx.numel(), z.size(1), act[0], act[1], y, table)
         ctx.save_for_backward(z, idx)
         ctx.act = act
         return y, table
@@ -296,17 +371,20 @@ class _ActScatter(torch.autograd.Function):
         z, idx = ctx.saved_tensors   # (autograd hands zeros for an output nobody used)
         dz = torch.empty_like(z)
         _call("act_scatter_backward", z, idx, idx.numel(), z.size(1), ctx.act[0], ctx.act[1], _f32(gy), _f32(gt), dz)
-        return dz, None, None, None
+        return dz, None, None, None, None
 
 
 class _ScatterAdd(torch.autograd.Function):
     """table[idx[m]] += rows[m] into a zeroed [R, W] table"""
 
     @staticmethod
-    def forward(ctx, rows, idx, R):
+    def forward(ctx, rows, idx, R, order=None):
         rows = _f32(rows)
         table = torch.zeros(R, rows.size(1), dtype=torch.float32, device=rows.device)
-        _call("scatter_add", table, idx, idx.numel(), rows.size(1), rows)
+        if _DET is not None:
+            _osum(_DET, table, idx, rows, order)
+        else:
+            _call("scatter_add", table, idx, idx.numel(), rows.size(1), rows)
         ctx.save_for_backward(idx)
         return table
 
@@ -316,7 +394,7 @@ class _ScatterAdd(torch.autograd.Function):
         g = _f32(g)
         out = torch.empty(idx.numel(), g.size(1), dtype=torch.float32, device=g.device)
         _call("gather_add", g, idx, idx.numel(), g.size(1), None, out)
-        return out, None, None
+        return out, None, None, None
 
 
 class _RowScale(torch.autograd.Function):
@@ -360,34 +438,26 @@ def _lin(X, W, c0=0, Kc=None, bias=None, base=None, act=None):
     return _Linear.apply(X, W, c0, Kc, bias, base, act)
 
 
-def _rows(X, idx):
+def _rows(X, idx, order=None):
     """X[idx] for a [R, w] table (also the 3-vector geometry: torch's own index backward sorts the indices per call)"""
-    return _GatherAdd.apply(X, idx, None)
+    return _GatherAdd.apply(X, idx, None, order)
 
 
-def _segment_sum(t, idx, R):
-    return _ScatterAdd.apply(t, idx, R)
-
-
-_WARNED_DET = False
-
-
-def _warn_deterministic(model):
-    """the wide path's segment sums and weight gradients are fp32 atomics in arrival order: say so once when the module was asked for
-    reproducible sums (`deterministic = True` is honoured by the fused kernels only)"""
-    global _WARNED_DET
-    # FastEGNN / FastRF keep the request in `_deterministic` (None: not asked), EGNN in a plain `deterministic` attribute
-    asked = model._deterministic if hasattr(model, "_deterministic") else getattr(model, "deterministic", False)
-    if asked is True and not _WARNED_DET:
-        import warnings
-        warnings.warn("fastegnn_amd: hidden_nf > 64 (or EGNN flat=True) runs on the unfused wide path, whose sums are fp32 atomics: "
-                      "results vary at rounding level from run to run although deterministic=True was requested", RuntimeWarning, stacklevel=3)
-        _WARNED_DET = True
+def _segment_sum(t, idx, R, order=None):
+    return _ScatterAdd.apply(t, idx, R, order)
 
 
 def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_mean, edge_attr=None, node_attr=None):
     """FastEGNN.forward (models/FastEGNN.py:255-276) for hidden_nf > 64 -> (node_loc, virtual_node_loc)."""
-    _warn_deterministic(model)
+    global _DET
+    prev, _DET = _DET, _ordered_of(model)
+    try:
+        return _forward(model, _DET, node_feat, node_loc, node_vel, edge_index, data_batch, loc_mean, edge_attr, node_attr)
+    finally:
+        _DET = prev
+
+
+def _forward(model, det, node_feat, node_loc, node_vel, edge_index, data_batch, loc_mean, edge_attr, node_attr):
     dev = node_loc.device
     Hn, C = model.hidden_nf, model.virtual_channels
     kind, p = model._act
@@ -407,6 +477,10 @@ def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_me
     idx_n = torch.arange(N, device=dev).repeat_interleave(C)                       # row n*C + c -> n
     col_sorted, col_perm = torch.sort(col, stable=True)          # once per graph: the column sums of every layer's backward as runs
     col_order = (col_sorted, col_perm)
+    # the ordered mode: the narrow [E, 3] gathers by col sum their gradient through col_order too, and data_batch is sorted (stably,
+    # once per forward) like col, so that a batch vector that is not monotone is still summed in a fixed order
+    ocol = col_order if det is not None else None
+    obatch = tuple(torch.sort(batch, stable=True)) if det is not None else None
     gravity = None
     if model.gravity is not None:
         # kept on the device between calls: torch.tensor(list, device=cuda) is a synchronous copy from pageable host memory, which a
@@ -445,11 +519,11 @@ def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_me
     for i in range(model.n_layers):
         g = getattr(model, "gcl_%d" % i)
         # ---- coord2radial (:176-185) and the virtual geometry (:200-201): 3-vectors, torch
-        cd = _rows(x, row) - _rows(x, col)
+        cd = _rows(x, row) - _rows(x, col, ocol)
         radial = (cd * cd).sum(1, keepdim=True)
         if model.normalize:
             cd = cd / (torch.sqrt(radial).detach() + 1e-8)
-        vcd = _rows(Z.reshape(B, 3 * C), batch).view(N, 3, C) - x.unsqueeze(-1)      # [N, 3, C]
+        vcd = _rows(Z.reshape(B, 3 * C), batch, obatch).view(N, 3, C) - x.unsqueeze(-1)      # [N, 3, C]
         vr = torch.norm(vcd, p=2, dim=1, keepdim=True)                              # [N, 1, C]
         # ---- edge_model (:102-108): Linear over cat[h[row], h[col], radial, edge_attr] = P[row] + Q[col] + feat . W[:, 2H:]
         W1 = g.edge_mlp[0].weight
@@ -462,24 +536,27 @@ def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_me
         z2 = _lin(pre, g.edge_mlp[2].weight, 0, Hn, g.edge_mlp[2].bias, None, A)
         fuse_sum = FUSE_ACT and not model.attention and not rf   # act and node_model's segment sum of it in one pass
         if fuse_sum:
-            m, agg_m = _ActScatter.apply(z2, row, N, A)                              # [E, H], [N, H]
+            m, agg_m = _ActScatter.apply(z2, row, N, A, None)                        # [E, H], [N, H]
         else:
             m = act(z2)                                                              # [E, H]
         if model.attention:
             m = _rowscale(m, torch.sigmoid(_lin(m, g.att_mlp[0].weight, 0, Hn, g.att_mlp[0].bias)))
         # ---- edge_mode_virtual (:111-119): rows (n, c); input cat[h, Hv[b], vr, m_X[b][:, c]]
-        cm = _segment_sum(x, batch, B) * inv_cnt_b.unsqueeze(1)               # global_mean_pool(coord)
+        cm = _segment_sum(x, batch, B, obatch) * inv_cnt_b.unsqueeze(1)       # global_mean_pool(coord)
         mX = Z - cm.unsqueeze(-1)
-        mX = torch.einsum('bij,bjk->bik', mX.permute(0, 2, 1), mX)                  # [B, C, C]
+        if det is not None:   # (a batched GEMM is the BLAS library's choice of kernel, split-K with atomics included: three-term sums here)
+            mX = (mX.permute(0, 2, 1).unsqueeze(3) * mX.unsqueeze(1)).sum(2)
+        else:
+            mX = torch.einsum('bij,bjk->bik', mX.permute(0, 2, 1), mX)              # [B, C, C]
         Wv = g.edge_mlp_virtual[0].weight
         Bc = _lin(mX.permute(0, 2, 1).reshape(B * C, C), Wv, 2 * Hn + 1, C, None, _lin(HvT, Wv, Hn, Hn))
         # rows (n, c) <- A[n] + Bc[b(n), c]: the second gather moves whole [C*H] rows by graph (its adjoint is then a segment sum
         # over sorted indices instead of N*C atomics onto B*C rows)
         pv = _Gather2.apply(_lin(h, Wv, 0, Hn, g.edge_mlp_virtual[0].bias), idx_n, None, None, vr.reshape(N * C, 1), Wv, 2 * Hn, None)
-        pv = _GatherAdd.apply(Bc.view(B, C * Hn), batch, pv.view(N, C * Hn)).view(N * C, Hn)
+        pv = _GatherAdd.apply(Bc.view(B, C * Hn), batch, pv.view(N, C * Hn), obatch).view(N * C, Hn)
         z2v = _lin(pv, g.edge_mlp_virtual[2].weight, 0, Hn, g.edge_mlp_virtual[2].bias, None, A)
         if fuse_sum:   # rows (n, c) of a node are one [C*H] row of graph batch[n]: node_model_virtual's pool as sorted runs
-            v, pool_v = _ActScatter.apply(z2v.view(N, C * Hn), batch, B, A)
+            v, pool_v = _ActScatter.apply(z2v.view(N, C * Hn), batch, B, A, obatch)
             v = v.view(N * C, Hn)
         else:
             v = act(z2v)                                                             # [N*C, H]
@@ -505,12 +582,12 @@ def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_me
             x_new = x_new + scalar_head(g.gravity_mlp, h) * gravity
         # ---- coord_model_virtual (:147-151)
         transX = vcd * s_vv.reshape(N, 1, C)
-        Z_new = Z + (_segment_sum(transX.reshape(N, 3 * C), batch, B) * inv_cnt_b.unsqueeze(1)).reshape(B, 3, C)
+        Z_new = Z + (_segment_sum(transX.reshape(N, 3 * C), batch, B, obatch) * inv_cnt_b.unsqueeze(1)).reshape(B, 3, C)
         if rf:   # the features of real and virtual nodes pass through (FastRF.py:186)
             x, Z = x_new, Z_new
             continue
         # ---- node_model (:154-166): Linear over cat[h, agg, flat(v), node_attr]; flat(v) of the reference is (h, c)-ordered
-        aggm = _rowscale(agg_m if fuse_sum else _ScatterAdd.apply(m, row, N), inv_cnt_row)
+        aggm = _rowscale(agg_m if fuse_sum else _ScatterAdd.apply(m, row, N, None), inv_cnt_row)
         W3 = g.node_mlp[0].weight
         W3v = W3[:, 2 * Hn:2 * Hn + Hn * C].reshape(W3.size(0), Hn, C).permute(0, 2, 1).reshape(W3.size(0), C * Hn)
         npre = _lin(aggm, W3, Hn, Hn, None, _lin(h, W3, 0, Hn, g.node_mlp[0].bias))
@@ -519,7 +596,7 @@ def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_me
             npre = _lin(node_attr.float(), W3, 2 * Hn + Hn * C, node_attr.size(1), None, npre)
         h_new = _lin(npre, g.node_mlp[2].weight, 0, Hn, g.node_mlp[2].bias, h if model.residual else None, A)
         # ---- node_model_virtual (:168-178)
-        poolV = _rowscale(pool_v if fuse_sum else _ScatterAdd.apply(v.view(N, C * Hn), batch, B), inv_cnt_b).view(B * C, Hn)
+        poolV = _rowscale(pool_v if fuse_sum else _ScatterAdd.apply(v.view(N, C * Hn), batch, B, obatch), inv_cnt_b).view(B * C, Hn)
         Wn = g.node_mlp_virtual[0].weight
         zv = _lin(poolV, Wn, Hn, Hn, None, _lin(HvT, Wn, 0, Hn, g.node_mlp_virtual[0].bias))
         HvT = _lin(zv, g.node_mlp_virtual[2].weight, 0, Hn, g.node_mlp_virtual[2].bias, HvT if model.residual else None, A)
@@ -530,7 +607,15 @@ def forward(model, node_feat, node_loc, node_vel, edge_index, data_batch, loc_me
 def egnn_forward(model, x, h, edge_index, edge_fea, v=None):
     """EGNN.forward (models/basic.py:337-341 over EGNN_Layer.forward :302-320) on the wide operators: hidden_nf > 64, or
     flat=True (every BaseMLP a Tanh MLP with 4 x hidden inner units, :176-178) -> (x, h)."""
-    _warn_deterministic(model)
+    global _DET
+    prev, _DET = _DET, _ordered_of(model)
+    try:
+        return _egnn_forward(model, _DET, x, h, edge_index, edge_fea, v)
+    finally:
+        _DET = prev
+
+
+def _egnn_forward(model, det, x, h, edge_index, edge_fea, v):
     dev = x.device
     Hn = model.hidden_nf
     kind, p = (K.ACT_TANH, 0.0) if model.flat else model._act
@@ -544,6 +629,7 @@ def egnn_forward(model, x, h, edge_index, edge_fea, v=None):
     f32 = dict(dtype=torch.float32, device=dev)
     inv_cnt = 1.0 / torch.zeros(N, **f32).index_add_(0, row, torch.ones(row.numel(), **f32)).clamp(min=1)   # aggregate(aggr='mean'), :27-52
     col_order = tuple(torch.sort(col, stable=True))
+    ocol = col_order if det is not None else None   # (the ordered mode: see forward)
     x = x.float()
     vv = v.float() if v is not None else None
     h = _lin(h.float(), model.embedding.weight, 0, model.in_node_nf, model.embedding.bias)
@@ -555,7 +641,7 @@ def egnn_forward(model, x, h, edge_index, edge_fea, v=None):
                     net.mlp[2].weight, 0, net.mlp[2].weight.size(1), net.mlp[2].bias, None, A)
 
     for layer in model.layers:
-        rij = _rows(x, row) - _rows(x, col)
+        rij = _rows(x, row) - _rows(x, col, ocol)
         scalar = (rij * rij).sum(1, keepdim=True)                                   # 1 x 1 Gram of the single vector, :268-270
         if model.norm:
             scalar = torch.nn.functional.normalize(scalar, p=2, dim=-1)
@@ -567,7 +653,7 @@ def egnn_forward(model, x, h, edge_index, edge_fea, v=None):
             pre = _lin(edge_fea.float(), W0, 1 + 2 * Hn, edge_fea.size(1), None, pre)
         zm = _lin(pre, net[2].weight, 0, net[2].weight.size(1), net[2].bias, None, A)
         if FUSE_ACT:
-            message, sum_message = _ActScatter.apply(zm, row, N, A)                   # [E, H], [N, H]
+            message, sum_message = _ActScatter.apply(zm, row, N, A, None)             # [E, H], [N, H]
         else:
             message = act(zm)
         f = rij * mlp(layer.coord_net, message)
@@ -575,7 +661,7 @@ def egnn_forward(model, x, h, edge_index, edge_fea, v=None):
         x_new = x + tot_f
         if vv is not None:
             x_new = x_new + mlp(layer.node_v_net, h) * vv
-        tot_message = _rowscale(sum_message if FUSE_ACT else _ScatterAdd.apply(message, row, N), inv_cnt)
+        tot_message = _rowscale(sum_message if FUSE_ACT else _ScatterAdd.apply(message, row, N, None), inv_cnt)
         Wn = layer.node_net.mlp[0].weight
         h = mlp(layer.node_net, None, _lin(tot_message, Wn, Hn, Hn, None, _lin(h, Wn, 0, Hn, layer.node_net.mlp[0].bias)))
         x = x_new

@@ -550,6 +550,7 @@ int fastegnn_scatter_add_rows(float *table, const int64_t *ids, int64_t n, int32
  *   linear_dx   dX[M,K] (+)= (G[M,O] . W[:, c0:c0+K]) * act'(Z[M,K])   -- Z NULL: no activation factor; with Z the result is the
  *               gradient of the pre-activation Z that `linear` took
  *   linear_dw   dW[:, c0:c0+K] += G^T act(X),  db += column sums of G (either may be NULL); fp32 atomics over row ranges
+ *               (linear_dw_ordered below: the same sums in a fixed order)
  *   head_dx / head_dw   the backward of the first Linear of a scalar head s = act(X W1^T + b1) . w2^T (coord_mlp_*, gravity_mlp:
  *               models/FastEGNN.py:55-99) from the head's output gradient gs[M]: G[m,o] = gs[m] w2[o] act'(Zc[m,o]) is formed in
  *               the kernels from the stored pre-activation Zc and never written; O (hidden width) a multiple of 4, O and K >= 9;
@@ -596,6 +597,41 @@ int fastegnn_wide_scatter_add_perm(float *table, const int64_t *idx_sorted, cons
                                    void *stream);
 int fastegnn_wide_rowscale(const float *X, const float *s, int64_t M, int32_t W, float *Y, void *stream);
 int fastegnn_wide_rowdot(const float *A, const float *B, int64_t M, int32_t W, float *out, void *stream);
+
+/* ---- the ORDERED forms of the wide path's sums (additive exports, revision unchanged) ----
+ * Every other wide entry point gives each output element to one thread that adds in a fixed order.  The sums above that do not --
+ * scatter_add, scatter_add_perm, act_scatter, linear_dw, head_dw: fp32 atomics in arrival order -- have the counterparts below, which
+ * use NO floating-point atomics: their results depend on (inputs, shapes) only, bit for bit, on any device, grid or occupancy.  The
+ * caller passes a workspace of at least the *_ws_bytes query, 16-byte aligned; its contents before and after a call mean nothing.  As
+ * everywhere in this header the library allocates nothing and never synchronises.
+ *
+ * segment_sum_ordered   table[t,:] = sum over the rows m with idx_sorted[m] == t of r(m), r(m) = act(rows[p(m),:]), p(m) = perm ?
+ *     perm[m] : m.  idx_sorted must be non-decreasing (a stable sort of an index plus the permutation that sorts it, or an index
+ *     that is sorted already with perm NULL).  act_kind = FASTEGNN_ACT_NONE and y NULL: rows as they are; act_kind >= 0: rows are
+ *     pre-activations, y[p(m),:] = act(rows[p(m),:]) is stored as well (the ordered act_scatter).  Rows of the table that idx_sorted
+ *     does not name are left as they were; a named row is OVERWRITTEN with its sum (callers zero-fill, so this is the += of
+ *     scatter_add on a zeroed table).  The order, per column: rps = 16, doubled while rps < 256 and ceil(M / rps) * W > 2^21.  Slot g
+ *     holds positions [g rps, min((g+1) rps, M)) of the sorted order.  Within a slot the terms of a run of equal targets are added
+ *     one by one in ascending position onto 0.f (fp32).  A run inside one slot is that sum.  A run over the slots g0 < .. < g1 is
+ *     ((s(g0) + s(g0+1)) + ..) + s(g1), s(g) the run's sum within slot g.  With a stable sort ascending position is input order.
+ *     Workspace: ceil(M / rps) * 2 * W floats.
+ * linear_dw_ordered / head_dw_ordered   the arguments and the += semantics of linear_dw / head_dw.  The rows are cut into nz
+ *     consecutive ranges, a function of (M, O, K) alone:
+ *       O > 8 and K > 8:   ns = min(ceil(512 / (ceil(O/128) ceil(K/128))), ceil(M / 256), floor(16 MiB / (4 (O K + 2 O)))), at least 1;
+ *                          rows = ceil(M / ns) rounded up to a multiple of 32; nz = ceil(M / rows)
+ *       otherwise:         ns = min(ceil(M / 512), 512, floor(4 MiB / (4 (O K + O)))), at least 1; rows = ceil(M / ns); nz = ceil(M / rows)
+ *     Each range's partial dW block, db and dw2 are stored to its own slab of the workspace (fp32; within a range the kernels add in
+ *     a fixed order of their own), then ONE thread per element adds the nz partials in ascending range order in double, rounds once to
+ *     fp32 and adds that to dW[o, c0 + k] / db[o] / dw2[o].  Workspace: nz (O K + 2 O) floats, nz (O K + O) in the small forms. */
+size_t fastegnn_wide_segment_sum_ws_bytes(int64_t M, int32_t W);
+int fastegnn_wide_segment_sum_ordered(float *table, const int64_t *idx_sorted, const int64_t *perm, int64_t M, int32_t W, const float *rows,
+                                      int32_t act_kind, float act_p, float *y, float *ws, size_t ws_bytes, void *stream);
+size_t fastegnn_wide_linear_dw_ws_bytes(int64_t M, int32_t O, int32_t K);
+int fastegnn_wide_linear_dw_ordered(const float *G, const float *X, int64_t M, int32_t O, int32_t K, float *dW, int32_t ldw, int32_t c0,
+                                    float *db, int32_t act_kind, float act_p, float *ws, size_t ws_bytes, void *stream);
+int fastegnn_wide_head_dw_ordered(const float *gs, const float *w2, const float *Zc, const float *X, int64_t M, int32_t O, int32_t K,
+                                  float *dW, int32_t ldw, int32_t c0, float *db, float *dw2, int32_t kind, float p, int32_t x_kind,
+                                  float x_p, float *ws, size_t ws_bytes, void *stream);
 
 /* ---- per-kernel timing with HIP events recorded on the launch stream (bench.py) ----
  * enable(1) brackets every kernel launch of this library with two events; collect() waits for
