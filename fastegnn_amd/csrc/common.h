@@ -43,22 +43,7 @@ __device__ __forceinline__ float dsilu_f(float z) {
 }
 // silu(z) and its derivative from ONE sigmoid: d = s*(1 + z*(1-s)) = s + y*(1-s) with y = z*s
 __device__ __forceinline__ void silu_both(float z, float &y, float &d) {
-#if defined(FE_SIGMOID_NEWTON) || defined(FE_EXP_ACCURATE)   // measured levers (round-2 verdict item 7), backward recompute only
-#ifdef FE_EXP_ACCURATE   // exp(-z) with the rounding error of the exp2 argument corrected (two fma + one fma)
-  const float t = -z * 1.44269504f;
-  const float lo = fmaf(-z, 1.44269504f, -t) + (-z) * 1.92596299e-8f;
-  const float e0 = __builtin_amdgcn_exp2f(t);
-  const float den = 1.0f + fmaf(e0, lo * 0.69314718f, e0);
-#else
-  const float den = 1.0f + __expf(-z);
-#endif
-  float s = __builtin_amdgcn_rcpf(den);
-#ifdef FE_SIGMOID_NEWTON   // one Newton step on the reciprocal
-  s = fmaf(fmaf(-den, s, 1.0f), s, s);
-#endif
-#else
   const float s = sigmoid_f(z);
-#endif
   y = z * s;
   d = s + y * (1.0f - s);
 }
@@ -181,30 +166,20 @@ __device__ __forceinline__ Vec vmul(const Vec &a, const Vec &b) {
   return vmap2(a, b, [](float x, float y) { return x * y; });
 }
 __device__ __forceinline__ Vec vscale(const Vec &a, float s) { return vmap(a, [s](float z) { return z * s; }); }
-// Element-wise forms: the f32x4 forms (-DFE_PACKED_VEC) lower to v_pk_fma_f32 / v_pk_add_f32, which the constants table of
+// Element-wise forms, one scalar instruction per element: the f32x4 forms lower to v_pk_fma_f32 / v_pk_add_f32, which the constants table of
 // MI355X_MICROARCH.md prices above the two plain instructions they replace when MFMAs are in flight.  Measured in round 4, two
 // repeats on one box: cfg4 step 10.988 -> 10.950 ms with the plain instructions (72 v_pk_fma_f32 -> 144 v_fmac_f32 in edge_fwd).
 __device__ __forceinline__ void vaxpy(Vec &acc, float s, const Vec &a) {
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-#ifndef FE_PACKED_VEC
+  for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc.t[t][r] = __builtin_fmaf(s, a.t[t][r], acc.t[t][r]);
-#else
-    acc.t[t] += s * a.t[t];
-#endif
-  }
 }
 __device__ __forceinline__ void vadd(Vec &acc, const Vec &a) {
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-#ifndef FE_PACKED_VEC
+  for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc.t[t][r] += a.t[t][r];
-#else
-    acc.t[t] += a.t[t];
-#endif
-  }
 }
 
 // natural-order 64-vector (bias, head weight, ...) -> this lane's 16 elements
@@ -246,36 +221,17 @@ __device__ __forceinline__ void vstore_u(float *base, unsigned off, const Vec &v
 // instruction + one add per step and no trip through the LDS crossbar (ds_bpermute, which is what __shfl_xor compiles to).
 // Same additions in the same order as the shuffle form: bitwise identical.  Inline assembly: the builtin's second result is
 // mis-modelled by this compiler (tools/scratch/permlane_test.hip pins the semantics on the GPU).  The partner lanes of a
-// q-sum hold the same item, so they are active together; -DFE_QSUM_SHFL restores the shuffles.)
+// q-sum hold the same item, so they are active together.)
 __device__ __forceinline__ float qsum(float p) {
-#ifdef FE_QSUM_SHFL
-  p += __shfl_xor(p, 16);
-  p += __shfl_xor(p, 32);
-  return p;
-#else
   float a = p, b = p;
   asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
   p = a + b;
   a = p; b = p;
   asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
   return a + b;
-#endif
 }
 // sum over the 16 items of a tile that share q: every lane of the 16-lane row gets the total.  DPP row rotations (pure
-// vector instructions; all lanes of the row must be active); -DFE_QSUM_SHFL: the xor butterfly through ds_bpermute.
-__device__ __forceinline__ float jsum_dpp(float p);
-__device__ __forceinline__ float jsum(float p) {
-#ifdef FE_QSUM_SHFL
-  p += __shfl_xor(p, 1);
-  p += __shfl_xor(p, 2);
-  p += __shfl_xor(p, 4);
-  p += __shfl_xor(p, 8);
-  return p;
-#else
-  return jsum_dpp(p);
-#endif
-}
-// same sum by DPP row rotations (no LDS crossbar traffic): every lane of the 16-lane row gets the total
+// vector instructions, no LDS crossbar traffic; all lanes of the row must be active).
 __device__ __forceinline__ float jsum_dpp(float p) {
   p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x128, 0xf, 0xf, false));  // row_ror:8
   p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x124, 0xf, 0xf, false));  // row_ror:4
@@ -283,6 +239,7 @@ __device__ __forceinline__ float jsum_dpp(float p) {
   p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x121, 0xf, 0xf, false));  // row_ror:1
   return p;
 }
+__device__ __forceinline__ float jsum(float p) { return jsum_dpp(p); }
 // Transposing sum over the 16 items of a tile: every lane holds 16 values (index k = 4t + r of a Vec); lane j of each
 // 16-lane row returns the total over the row's 16 lanes of value j.  A butterfly that halves the number of values per
 // step.  Steps 1, 2: partners 8 and 4 lanes away (row shifts); the half a lane keeps depends on lane bits 3 / 2, i.e. on
@@ -403,14 +360,6 @@ __device__ __forceinline__ void gemm64(const float *img, const Vec &in, Vec &acc
   }
 }
 
-// gemm64 between scheduling fences: the operand reads of ONE layer are in flight at a time.  Without the
-// fences the scheduler hoists the image reads of every following layer of a tile (64 registers each).
-__device__ __forceinline__ void gemm64_f(const float *img, const Vec &in, Vec &acc) {
-  __builtin_amdgcn_sched_barrier(0);
-  gemm64(img, in, acc);
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 // ---- 3-way bf16 split ("bf16x3") variant of gemm64 ------------------------------------------
 // fp32-input MFMA shares the vector ALUs with every other VALU instruction and runs at 1/16 of the
 // bf16 matrix rate.  x = h + m + l with h, m, l bf16 values (8+8+8 mantissa bits, each the round-to-nearest
@@ -426,35 +375,23 @@ struct Split {
   u32x4 p[3][2];   // [part h|m|l][k-step] : 8 bf16 per lane
 };
 __device__ __forceinline__ unsigned f2u(float x) { return __builtin_bit_cast(unsigned, x); }
-__device__ __forceinline__ float trunc_bf(float x) { return __builtin_bit_cast(float, f2u(x) & 0xffff0000u); }
-// {bf16(x0) in the low half, bf16(x1) in the high half}, by truncation
-__device__ __forceinline__ unsigned pack_hi(float x0, float x1) {
-  return __builtin_amdgcn_perm(f2u(x1), f2u(x0), 0x07060302u);
-}
 // One level of the h | m | l split of a pair: returns the packed bf16 parts of (a0, a1) and leaves the residuals in them.
 // Round to nearest even: one v_cvt_pk_bf16_f32 per pair, shift / and + sub per element -- the instruction count of the
-// truncating split of rounds 1-2 (and + sub per element, one perm per pair; -DFE_SPLIT_TRUNC brings it back).  With
+// truncating split of rounds 1-2 (and + sub per element, one perm per pair).  With
 // truncation every part has the sign of the value, so the dropped m*l, l*m, l*l terms and the last residue all point
-// towards zero: a bias of ~1e-7 per product that does not cancel in cancelling sums.  Measured on one box (round 3,
-// tools/gpu_lever_newton.sh): 40 -> 32 gradient comparisons beyond 2 x ref + 1e-6, the attention goldens' excesses down by
+// towards zero: a bias of ~1e-7 per product that does not cancel in cancelling sums.  Measured on one box (round 3):
+// 40 -> 32 gradient comparisons beyond 2 x ref + 1e-6, the attention goldens' excesses down by
 // 2-4 x (att_mlp.0.bias 2.67e-5 -> 6.8e-6), for +0.5 % step time (v_cvt_pk_bf16_f32 issues in 4-5 cycles, v_perm_b32 in 4).
 __device__ __forceinline__ unsigned part_pack(float &a0, float &a1) {
-#ifndef FE_SPLIT_TRUNC
   typedef float f32x2_ __attribute__((ext_vector_type(2)));
   typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
   const unsigned p = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_{a0, a1}, bf16x2_));
   a0 -= __builtin_bit_cast(float, p << 16);
   a1 -= __builtin_bit_cast(float, p & 0xffff0000u);
   return p;
-#else
-  const unsigned p = pack_hi(a0, a1);
-  a0 -= trunc_bf(a0);
-  a1 -= trunc_bf(a1);
-  return p;
-#endif
 }
-// k index held by element e of lane quarter q in k-step s (matches the chained D layout)
-__host__ __device__ __forceinline__ int bf3_k(int s, int q, int e) { return 16 * (2 * s + (e >> 2)) + 4 * q + (e & 3); }
+// bf3_k, the k index held by element e of lane quarter q in k-step s (matches the chained D layout):
+// 16 * (2 * s + (e >> 2)) + 4 * q + (e & 3)
 // u32 index of (part, out o, k) in a split image; pairs (e, e+1) share a word
 __host__ __device__ __forceinline__ int img3_index(int part, int o, int k) {
   const int t = o >> 4, i = o & 15, tile = k >> 4, q = (k >> 2) & 3, r = k & 3;
@@ -488,26 +425,6 @@ __device__ __forceinline__ Split vsplit(const Vec &v) {
 // (fragments of group g+1 requested ahead of the MFMAs of group g: see gemm64_x3_rm)
 __device__ __forceinline__ void gemm64_x3(const unsigned *img3, const Split &in, Vec &acc) {
   const u32x4 *ip = reinterpret_cast<const u32x4 *>(img3) + lane_id();
-#ifdef FE_NO_GEMM_PIPE
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const bf16x8 ah = __builtin_bit_cast(bf16x8, ip[(t * 2 + s) * 64]);
-      const bf16x8 am = __builtin_bit_cast(bf16x8, ip[512 + (t * 2 + s) * 64]);
-      const bf16x8 al = __builtin_bit_cast(bf16x8, ip[1024 + (t * 2 + s) * 64]);
-      const bf16x8 xh = __builtin_bit_cast(bf16x8, in.p[0][s]);
-      const bf16x8 xm = __builtin_bit_cast(bf16x8, in.p[1][s]);
-      const bf16x8 xl = __builtin_bit_cast(bf16x8, in.p[2][s]);
-      // smallest terms first: (weight part, activation part) = (l,h) (m,m) (h,l) | (m,h) (h,m) | (h,h)
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, xm, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, xh, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xm, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc.t[t], 0, 0, 0);
-    }
-#else
   __builtin_amdgcn_sched_barrier(0);
   u32x4 fr[2][3];
 #pragma unroll
@@ -537,40 +454,8 @@ __device__ __forceinline__ void gemm64_x3(const unsigned *img3, const Split &in,
     __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // 6 MFMAs
   }
   __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 __device__ __forceinline__ void gemm64_x3(const unsigned *img3, const Vec &in, Vec &acc) { gemm64_x3(img3, vsplit(in), acc); }
-
-// Diagnostic lever (-DFE_EDGE_T2, edge_fwd only): the activation operand split into TWO bf16 parts
-// (h, m: 16 mantissa bits) -- 3.5 instead of 5.5 vector instructions per element and five products instead of six (the
-// (h, l) product is gone).  Costs 2^-17 relative on the operand; measured in DESIGN.md section 12, not used by any product path.
-__device__ __forceinline__ void gemm64_x3_t2(const unsigned *img3, const Vec &v, Vec &acc) {
-  const u32x4 *ip = reinterpret_cast<const u32x4 *>(img3) + lane_id();
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float x[8];
-    u32x4 ph, pm;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[e] = v.t[2 * s + (e >> 2)][e & 3];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {   // (part_pack: the rounding mode of the three-part split, nearest since late round 3)
-      ph[w] = part_pack(x[2 * w], x[2 * w + 1]);
-      pm[w] = part_pack(x[2 * w], x[2 * w + 1]);
-    }
-    const bf16x8 xh = __builtin_bit_cast(bf16x8, ph), xm = __builtin_bit_cast(bf16x8, pm);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const bf16x8 ah = __builtin_bit_cast(bf16x8, ip[(t * 2 + s) * 64]);
-      const bf16x8 am = __builtin_bit_cast(bf16x8, ip[512 + (t * 2 + s) * 64]);
-      const bf16x8 al = __builtin_bit_cast(bf16x8, ip[1024 + (t * 2 + s) * 64]);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, xm, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, xh, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xm, acc.t[t], 0, 0, 0);
-      acc.t[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc.t[t], 0, 0, 0);
-    }
-  }
-}
 
 // ---- bf16 operand mode (FASTEGNN_F_BF16): both operands rounded to bf16 (RNE), ONE bf16 product, fp32 accumulate ----
 // The weights are rounded by pack_kernel, so the `h` part of a split image IS the bf16 weight matrix (m = l = 0) and
@@ -581,11 +466,6 @@ __device__ __forceinline__ unsigned pack_rne(float x0, float x1) {   // {bf16(x0
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
 }
 __device__ __forceinline__ float round_bf(float x) { return (float)(__bf16)x; }
-__host__ __device__ __forceinline__ float round_bf_host(float x) {   // same rounding by integer arithmetic (finite x)
-  unsigned u = __builtin_bit_cast(unsigned, x);
-  u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-  return __builtin_bit_cast(float, u);
-}
 struct BfOp {
   u32x4 p[2];   // [k-step] : 8 bf16 per lane, the k order of the split images (bf3_k)
 };
@@ -642,10 +522,6 @@ __device__ __forceinline__ bf16x8 rm_frag(const char *img, int part, int t, int 
     hi = lds_tr_read(p + 16 * RM_RS);
   } else {
     const char *p = img + part * RM_PART + (16 * t + i) * RM_RS + (32 * s + 4 * q) * 2;
-#ifdef FE_RM_READ2
-    lo = *reinterpret_cast<const u32x2 *>(p);
-    hi = *reinterpret_cast<const u32x2 *>(p + 32);
-#else
     // Two ds_read_b64 (conflict-free on the 144-byte rows, 2 LDS cycles each).  As plain loads the compiler fuses them --
     // and the loads of neighbouring fragments -- into ds_read2_b64, which is banked modulo 32 dwords: rows i and i + 8 of
     // a 16-lane group then collide (2-way) and the instruction runs at half the rate; the counters showed a third of the
@@ -654,7 +530,6 @@ __device__ __forceinline__ bf16x8 rm_frag(const char *img, int part, int t, int 
     typedef __attribute__((address_space(3))) const volatile u32x2 *lds_vu32x2;
     lo = *(lds_vu32x2)(p);
     hi = *(lds_vu32x2)(p + 32);
-#endif
   }
   return __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], hi[0], hi[1]});
 }
@@ -662,16 +537,11 @@ __device__ __forceinline__ bf16x8 rm_frag(const char *img, int part, int t, int 
 // requested BEFORE the six MFMAs of group g are issued (sched_group_barrier pins the order; the compiler's own schedule was
 // "6 MFMA, 6 reads, wait" -- every group then waited a full LDS round trip with an idle matrix pipe behind it).  Costs 12
 // more live registers: PIPE = false (edge_bwd_pc_kernel, whose producers are at their register limit: 10 spilled registers
-// and 3.29 instead of 3.21 ms per step with it) or -DFE_NO_GEMM_PIPE restore the compiler's order.  Measured on one box
+// and 3.29 instead of 3.21 ms per step with it) restores the compiler's order.  Measured on one box
 // (tools/gpu_ab.sh): virt_bwd 4.15 -> 3.94 ms per step, virt_fwd 1.81 -> 1.77.
 template <bool TR, bool PIPE = true>
 __device__ __forceinline__ void gemm64_x3_rm(const char *img, const Split &in, Vec &acc) {
-#ifdef FE_NO_GEMM_PIPE
-  constexpr bool pipe = false;
-#else
-  constexpr bool pipe = PIPE;
-#endif
-  if constexpr (!pipe) {
+  if constexpr (!PIPE) {
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -777,7 +647,7 @@ __device__ __forceinline__ void part2_pack(float a0, float a1, unsigned &ph, uns
   asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h), "v"(a0));
   asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h), "v"(a1));
   unsigned l;
-  // (ends with the VALU -> MFMA-operand wait states: the weight images go to memory, but edge_fwd32.hip feeds these to MFMAs; see vsplit2)
+  // (ends with the VALU -> MFMA-operand wait states: the weight images go to memory, but a caller may feed these to MFMAs; see vsplit2)
   asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\tv_fma_mixhi_f16 %0, %2, %3, 0\n\ts_nop 1" : "=&v"(l) : "v"(r0), "v"(r1), "s"(F2_UP));
   ph = h;
   pl = l;
@@ -1302,25 +1172,6 @@ __device__ __forceinline__ typename OperandOf<MODE>::type make_operand(const Vec
   else if constexpr (MODE == GM_F16) return vsplit2(v);
   else return v;
 }
-// ---- the 32-edge forward kernel (edge_fwd32.hip): does this build have it, and where its images live ----
-// Measured, NOT adopted (profiles/r05_lever_edge_fwd32.txt): the 32-edge kernel issues 11 % fewer cycles per edge but runs two waves per
-// SIMD (242-256 registers) where the 16-edge kernel runs four, and loses more to exposed MFMA / LDS latency than it saves:
-// 0.837 against 0.797 ms per step on one box.  -DFE_EDGE_FWD32=1 builds it in (and makes pack_kernel write its images).
-#ifndef FE_EDGE_FWD32
-#define FE_EDGE_FWD32 0
-#endif
-#ifdef FE_ACT_GENERIC
-constexpr bool EDGE_FWD32 = false;
-#else
-constexpr bool EDGE_FWD32 = FE_EDGE_FWD32 != 0 && (FE_FWD_F16 & 1) != 0 && LOG2E_FOLD_FIRST;
-#endif
-// u32 index (two fp16: contraction indices k, k + 1, k even) of W[o][k] in an f16x2 image of the 32x32x16 operand layout:
-// part h at 0, part l at 2048; lane (i, hf) of output block bo, k-step s reads its 8 values as one 16-byte word group
-__host__ __device__ inline int img32_word(int part, int o, int k) {
-  const int bo = o >> 5, i = o & 31, b = k >> 5, g = (k >> 3) & 3, hf = (k >> 2) & 1, r = k & 3;
-  const int s = 2 * b + (g >> 1), e = 4 * (g & 1) + r;
-  return part * 2048 + ((bo * 4 + s) * 64 + hf * 32 + i) * 4 + (e >> 1);
-}
 // image i of a resident image array (fp32 images for GM_F32, split images otherwise)
 template <int MODE, bool PIPE = false>
 __device__ __forceinline__ void gemm_op(const void *img, int i, const typename OperandOf<MODE>::type &in, Vec &acc) {
@@ -1329,8 +1180,6 @@ __device__ __forceinline__ void gemm_op(const void *img, int i, const typename O
   else if constexpr (MODE == GM_F16) gemm64_f2<PIPE>(reinterpret_cast<const unsigned *>(img) + i * IMG3, in, acc);
   else gemm64(reinterpret_cast<const float *>(img) + i * IMG, in, acc);
 }
-// a product on an fp32 image (fp32-input MFMA) inside a kernel of form MODE: in bf16 mode the activation is rounded
-// (the image already holds bf16-representable weights), so the product has the bf16-mode semantics exactly
 // product (TR = false) or transposed product (TR = true) on a row-major split image, forms GM_X3 / GM_BF16
 // (PIPE: the hand-pipelined order of the bf16x3 form, P16: of the f16x2 form -- separate switches, the two forms differ by 32 registers)
 template <int MODE, bool TR, bool PIPE = true, bool P16 = true>
@@ -1347,11 +1196,6 @@ template <int MODE, bool TR, bool PIPE = true, bool P16 = true>
 __device__ __forceinline__ void gemm_rm_g(const char *img, const typename GradOperandOf<MODE>::type &in, Vec &acc) {
   if constexpr (MODE == GM_F16) gemm64_f2_rm_<TR, true, P16>(img, in.s, in.inv, acc);
   else gemm_rm<MODE, TR, PIPE>(img, in, acc);
-}
-template <int MODE>
-__device__ __forceinline__ void gemm64_m(const float *img, const Vec &in, Vec &acc) {
-  if constexpr (MODE == GM_BF16) gemm64(img, vround(in), acc);
-  else gemm64(img, in, acc);
 }
 
 // cooperative copy of n_img consecutive images global -> LDS (16-byte moves)

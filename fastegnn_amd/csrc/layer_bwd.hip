@@ -4,18 +4,12 @@
 // operands of the 64x64 weight gradients are written once ([rows,64]) and contracted by the
 // generic wgrad_tn kernel (misc.hip).
 #include "stages.h"
-#ifdef FE_DIAG_NOSTORE
-#define WG_STORE(x)
-#else
-#define WG_STORE(x) x
-#endif
 
 namespace fe {
 
 __device__ __forceinline__ Vec vdsilu_mul(const Vec &g, const Vec &z FE_ACT_P) {
   return vmap2(g, z, [=](float a, float b) { return a * dsilu_f(b FE_ACT_A); });
 }
-__device__ __forceinline__ Vec vmask(const Vec &v, bool keep) { return keep ? v : vzero(); }
 
 // Rank-1 weight gradients are accumulated per lane (D layout) over a wave's tiles.  At kernel end
 // they are summed over the 16 items of the tile (shuffles), over the workgroup's waves (LDS) and
@@ -254,7 +248,7 @@ struct EdgeBwdArgs {
 // Eight waves: waves are dealt round-robin to the four SIMDs, so waves 3 and 7 share SIMD 3 and have it to themselves --
 // they are the two CONSUMERS, one per ring (wave 3: edge_mlp.2, wave 7: coord_mlp_r.0); the six producers sit two per SIMD
 // on SIMDs 0..2.  A single consumer serving both rings was latency-exposed (dependent LDS reads -> split -> MFMA chain at
-// one wave on its SIMD): with the contractions skipped the kernel ran 18 % faster (-DFE_DIAG_NOCONS).
+// one wave on its SIMD): with the contractions skipped the kernel ran 18 % faster.
 // -DFE_PC_WAVES=12 (round 6 experiment): three waves per SIMD -- ten producers (waves 0,1,2,4,5,6,8,9,10,11) + the two consumers, 168 registers
 #ifndef FE_PC_WAVES
 #define FE_PC_WAVES 8
@@ -460,14 +454,6 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
         while (lds_ld(&ctrl[PC_FILLED + kind * PC_RING + s1]) != r1w + 1) __builtin_amdgcn_s_sleep(2);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");   // the slot reads stay behind the flag reads
       const float *g0 = ring + (kind * PC_RING + s0) * PC_SLOT, *g1 = ring + (kind * PC_RING + s1) * PC_SLOT;
-#ifdef FE_DIAG_NOCONS   // diagnostic: the consumer only drains its slots (is the kernel consumer-bound?)
-      if (l == 0) {
-        lds_st(&ctrl[PC_DRAINED + kind * PC_RING + s0], r0w + 1);
-        if (two) lds_st(&ctrl[PC_DRAINED + kind * PC_RING + s1], r1w + 1);
-      }
-      (void)g0; (void)g1; (void)acc; (void)bs;
-      return;
-#endif
       // every value of the two slots is read first and the slots are handed back BEFORE the splits and products: with
       // two slots per ring the producers otherwise wait out the whole contraction (their `publish` phases were 17 % of
       // the producer time in the stamps)
@@ -700,11 +686,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
         xv[ee] = pt[ee * TS + H + (l & 3)];
       }
       const int rowv = S.row;
-#ifdef FE_DIAG_NOATOMIC   // diagnostic (wrong col-side gradients): what do the scatter atomics cost the producers?  (round 6: 14 % of the kernel)
-      if (false) {
-#else
-      if (A.g_QXs_atomic) {   // default (no FASTEGNN_F_DETERMINISTIC): one coalesced 256-byte atomic row per edge ...
-#endif
+      if (A.g_QXs_atomic) {   // default (no FASTEGNN_F_DETERMINISTIC): one coalesced 256-byte atomic row per edge ...  (round 6: these atomics are 14 % of the kernel)
         const int colv = S.col;
         char *gb = reinterpret_cast<char *>(A.g_QXs_atomic);   // wave-uniform base + 32-bit lane offsets (tables < 2^30 floats)
         const unsigned lo = 4u * (unsigned)l;
@@ -723,20 +705,13 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
         if (l < 3 * nvalid) atomicAdd(reinterpret_cast<float *>(gb + (cx * (QXLD * 4u) + 4u * (unsigned)(H + kx))), -gx);
       }
       // row changes inside the tile from one DPP compare + ballot (as in edge_fwd_kernel); the row id is read only at a change
-#ifndef FE_WALK_READLANE
       const int prevrow = __builtin_amdgcn_update_dpp(rowv, rowv, 0x111, 0xf, 0xf, false);   // row_shr:1
       const unsigned starts = (unsigned)__builtin_amdgcn_ballot_w64(j == 0 ? rowv != cur : rowv != prevrow) & 0xffffu;
-#endif
 #pragma unroll
       for (int ee = 0; ee < 16; ++ee) {
         if (ee < nvalid) {
-#ifndef FE_WALK_READLANE
           if ((starts >> ee) & 1u) {
             const int rw = __builtin_amdgcn_readlane(rowv, ee);
-#else
-          const int rw = __builtin_amdgcn_readlane(rowv, ee);
-          if (rw != cur) {
-#endif
             if (cur >= 0) flush();
             zero_rows(cur >= 0 ? cur + 1 : r0, rw);
             cur = rw;

@@ -322,21 +322,14 @@ __global__ __launch_bounds__(64 * EDGE_FWD_WAVES) void edge_fwd_kernel(EdgeArgs 
         const int rowv = S.row;
         // where the row changes inside the tile: ONE lane compare with the lane below (DPP) and a ballot instead of sixteen
         // v_readlane + scalar compares; the row id itself is read only at a change (~2 per tile at degree 19)
-#ifndef FE_WALK_READLANE
         const int prevrow = __builtin_amdgcn_update_dpp(rowv, rowv, 0x111, 0xf, 0xf, false);   // row_shr:1 (lane 0 of a row keeps its own)
         const unsigned long long chg = __builtin_amdgcn_ballot_w64(j == 0 ? rowv != cur : rowv != prevrow);
         const unsigned starts = (unsigned)chg & 0xffffu;      // lanes 0..15 (q = 0): one bit per edge of the tile
-#endif
 #pragma unroll
         for (int ee = 0; ee < 16; ++ee) {
           if (ee < nvalid) {
-#ifndef FE_WALK_READLANE
             if ((starts >> ee) & 1u) {
               const int rw = __builtin_amdgcn_readlane(rowv, ee);
-#else
-            const int rw = __builtin_amdgcn_readlane(rowv, ee);
-            if (rw != cur) {
-#endif
               if (cur >= 0) flush();
               zero_rows(cur >= 0 ? cur + 1 : r0, rw);
               cur = rw;
@@ -374,9 +367,6 @@ int edge_forward(const fastegnn_layer_t *L, hipStream_t st) {
   EdgeArgs a = make_edge_args(L);
   FE_REQUIRE((size_t)L->N * QXLD < (1u << 30) && (size_t)g.n_src * QXLD < (1u << 30) && (size_t)g.n_edges * 8 < (1u << 30),
              "edge_forward: tables exceed the 32-bit offset range of the gather path");
-#if FE_EDGE_FWD32   // the 32-edge lever kernel (edge_fwd32.hip) is only part of a `make lever32` build
-  if (edge_forward32_applies(L)) return edge_forward32(L, st);
-#endif
   // one workgroup per CU once there are >= 256 x 16 row chunks; small graphs spread their chunks (32 edges) over as
   // many waves as there are chunks instead of serialising them in a few workgroups (the N-body mini-batches)
   int grid = cdiv(g.n_chunks, EDGE_FWD_WAVES);

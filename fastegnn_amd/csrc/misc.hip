@@ -115,167 +115,10 @@ __global__ void build_batch_kernel(const int64_t *b64, int N, int B, int32_t *ba
 // The kernel streams its operands at ~4.0 TB/s against 5.3 TB/s for a bare read loop on this part
 // (fastegnn_selftest_stream): it is HBM-bound, and a bf16x3 version of the inner product (6x fewer
 // MFMA issue cycles) measured the same in round 1 (6.0 ms per step) and again in round 2 on the bundle geometry
-// (2.93 vs 2.91 ms per step) -- the fp32-input MFMA form is kept.
-constexpr int WTS = 80;  // LDS row stride of the staged operand tiles (conflict-free b32 column reads)
+// (2.93 vs 2.91 ms per step) -- the matrix-pipe form below is the one built.
 #ifndef FE_WG_OCC
 #define FE_WG_OCC 2   // waves per SIMD the contraction kernels are compiled for (measured per step: 2 -> 2.84 ms, 3 -> 2.94 ms with 44-52 B of scratch, 4 -> 5.8 ms)
 #endif
-
-// rows [m_first, m1) of one (G, T) pair in steps of `step` rows, 16 rows at a time, into the wave's 64x64 accumulator
-// (acc[ti][tk][r] = dW[16ti + 4q + r][16tk + i]); gt / tt: this wave's two 16 x WTS staging tiles.
-// lane l loads 16 bytes of row (4s + q), columns 4i..4i+3: full 256-byte lines per row.  Addresses are a
-// wave-uniform base (row m) plus loop-invariant 32-bit lane offsets: no per-load VALU math.
-__device__ __forceinline__ void wg_accumulate(const float *G, const float *T, int ldg, int ldt, long m_first, long m1,
-                                              int step, bool want_bias, bool rnd, float *gt, float *tt,
-                                              f32x4 (&acc)[4][4], float (&bsum)[4]) {
-  const int l = lane_id(), i = l & 15, q = l >> 4;
-  f32x4 gv[4], tv[4];
-  unsigned og[4], ot[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    og[s] = ((unsigned)(4 * s + q) * (unsigned)ldg + 4u * i) * 4u;
-    ot[s] = ((unsigned)(4 * s + q) * (unsigned)ldt + 4u * i) * 4u;
-  }
-  auto issue = [&](long m) {
-    const char *gb = reinterpret_cast<const char *>(G + (size_t)m * ldg);
-    const char *tb = reinterpret_cast<const char *>(T + (size_t)m * ldt);
-    if (m + 16 <= m1) {   // full tile (wave-uniform): unmasked loads
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        gv[s] = *reinterpret_cast<const f32x4 *>(gb + og[s]);
-        tv[s] = *reinterpret_cast<const f32x4 *>(tb + ot[s]);
-      }
-    } else {              // ragged tail: rows beyond m1 read row m (always valid) and are zeroed below
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const bool ok = m + 4 * s + q < m1;
-        gv[s] = *reinterpret_cast<const f32x4 *>(gb + (ok ? og[s] : 4u * i * 4u));
-        tv[s] = *reinterpret_cast<const f32x4 *>(tb + (ok ? ot[s] : 4u * i * 4u));
-      }
-    }
-  };
-  long m = m_first;
-  if (m < m1) issue(m);
-  for (; m < m1; m += step) {
-    __builtin_amdgcn_wave_barrier();
-    if (m + 16 <= m1) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        *reinterpret_cast<f32x4 *>(gt + (4 * s + q) * WTS + 4 * i) = gv[s];
-        *reinterpret_cast<f32x4 *>(tt + (4 * s + q) * WTS + 4 * i) = tv[s];
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const bool ok = m + 4 * s + q < m1;
-        *reinterpret_cast<f32x4 *>(gt + (4 * s + q) * WTS + 4 * i) = ok ? gv[s] : f32x4{0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<f32x4 *>(tt + (4 * s + q) * WTS + 4 * i) = ok ? tv[s] : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (m + step < m1) issue(m + step);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      float av[4], bv[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        av[t] = gt[(4 * s + q) * WTS + 16 * t + i];
-        bv[t] = tt[(4 * s + q) * WTS + 16 * t + i];
-      }
-      if (rnd) {   // bf16 operand mode (wave-uniform): products of bf16 values are exact in fp32-input MFMA
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          if (want_bias) bsum[t] += av[t];   // the bias gradient sums the unrounded rows
-          av[t] = round_bf(av[t]);
-          bv[t] = round_bf(bv[t]);
-        }
-      }
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti) {
-        if (want_bias && !rnd) bsum[ti] += av[ti];
-#pragma unroll
-        for (int tk = 0; tk < 4; ++tk)
-          acc[ti][tk] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ti], bv[tk], acc[ti][tk], 0, 0, 0);
-      }
-    }
-  }
-}
-
-// The same contraction with the MFMA fragments loaded straight from global memory (lane l = i + 16 k reads element
-// (row m + 4 s + k, column 16 t + i): exactly the 16x16x4 operand layout, 64-byte segments of four rows per instruction), no
-// LDS staging: nothing to write, read back or fence, and DEPTH tiles of loads in flight per wave instead of one.
-#ifndef FE_WG_DEPTH
-#define FE_WG_DEPTH 2
-#endif
-__device__ __forceinline__ void wg_accumulate_direct(const float *G, const float *T, int ldg, int ldt, long m_first, long m1,
-                                                     int step, bool want_bias, bool rnd, f32x4 (&acc)[4][4], float (&bsum)[4]) {
-  constexpr int D = FE_WG_DEPTH;
-  const int l = lane_id(), i = l & 15, k = l >> 4;
-  float gv[D][16], tv[D][16];
-  unsigned og[4], ot[4];   // byte offsets of (row 4 s + k, column i); + 64 t bytes per column tile
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    og[s] = ((unsigned)(4 * s + k) * (unsigned)ldg + (unsigned)i) * 4u;
-    ot[s] = ((unsigned)(4 * s + k) * (unsigned)ldt + (unsigned)i) * 4u;
-  }
-  auto issue = [&](int slot, long m) {
-    const char *gb = reinterpret_cast<const char *>(G + (size_t)m * ldg);
-    const char *tb = reinterpret_cast<const char *>(T + (size_t)m * ldt);
-    const bool full = m + 16 <= m1;   // wave-uniform; a ragged tail reads row m (always valid) and is zeroed at use
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const bool ok = full || m + 4 * s + k < m1;
-      const unsigned a = ok ? og[s] : (unsigned)i * 4u, b = ok ? ot[s] : (unsigned)i * 4u;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        gv[slot][4 * s + t] = *reinterpret_cast<const float *>(gb + a + 64u * t);
-        tv[slot][4 * s + t] = *reinterpret_cast<const float *>(tb + b + 64u * t);
-      }
-    }
-  };
-  auto consume = [&](int slot, long m) {
-    const bool full = m + 16 <= m1;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      float av[4], bv[4];
-      const bool ok = full || m + 4 * s + k < m1;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        av[t] = ok ? gv[slot][4 * s + t] : 0.f;
-        bv[t] = ok ? tv[slot][4 * s + t] : 0.f;
-      }
-      if (rnd) {   // bf16 operand mode (wave-uniform): products of bf16 values are exact in fp32-input MFMA
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          if (want_bias) bsum[t] += av[t];   // the bias gradient sums the unrounded rows
-          av[t] = round_bf(av[t]);
-          bv[t] = round_bf(bv[t]);
-        }
-      }
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti) {
-        if (want_bias && !rnd) bsum[ti] += av[ti];
-#pragma unroll
-        for (int tk = 0; tk < 4; ++tk)
-          acc[ti][tk] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ti], bv[tk], acc[ti][tk], 0, 0, 0);
-      }
-    }
-  };
-  long m = m_first;
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-    if (m + (long)d * step < m1) issue(d, m + (long)d * step);
-  while (m < m1) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {   // static slots: the ring is the unrolled loop body
-      if (m < m1) {
-        consume(d, m);
-        if (m + (long)D * step < m1) issue(d, m + (long)D * step);
-        m += step;
-      }
-    }
-  }
-}
 
 // The contraction on the bf16 matrix pipe: 32 rows per step, fragments straight from global memory in the 16x16x32 operand
 // layout (lane l = i + 16 q holds rows m + 8 q .. + 7 of column 16 t + i: eight 64-byte-segment loads per fragment), each
@@ -392,15 +235,8 @@ __device__ __forceinline__ void wg_accumulate_x3(const float *G, const float *T,
 }
 
 __global__ __launch_bounds__(256, FE_WG_OCC) void wgrad_tn_kernel(WgTable tab) {
-  // staged form: 40 KB of staging tiles, the 64x64 reduction buffer aliases them after the main loop; default form: the
-  // four waves' partial tiles (64 KB)
-#if defined(FE_WG_STAGED)
-  __shared__ __attribute__((aligned(16))) float smem[4 * 2 * 16 * WTS];
-#else
-  __shared__ __attribute__((aligned(16))) float smem[4 * IMG];
-#endif
+  __shared__ __attribute__((aligned(16))) float smem[4 * IMG];   // the four waves' partial tiles (64 KB)
   __shared__ float redb[H];
-  float *red = smem;
   // locate the job of this workgroup
   int jb = 0;
 #pragma unroll 1
@@ -408,16 +244,7 @@ __global__ __launch_bounds__(256, FE_WG_OCC) void wgrad_tn_kernel(WgTable tab) {
   const WgJob &a = tab.job[jb];
   const int local = blockIdx.x - a.wg_begin;
   // batch index varies fastest: co-resident workgroups read the same row range of every batch slice
-  int bidx = local % a.nb, split = local / a.nb;
-#ifdef FE_WG_XCD
-  // ... and the nb workgroups of one row range sit on ONE XCD (workgroup i runs on XCD i % 8): the G rows they share are
-  // then served by that XCD's L2 instead of being fetched once per XCD
-  if (a.nb > 1 && (a.nsplit & 7) == 0 && (a.wg_begin & 7) == 0) {
-    const int xcd = local & 7, slot = local >> 3;
-    bidx = slot % a.nb;
-    split = xcd + 8 * (slot / a.nb);
-  }
-#endif
+  const int bidx = local % a.nb, split = local / a.nb;
   const int l = lane_id(), i = l & 15, q = l >> 4, w = wave_id();
   const float *G = a.G + (size_t)bidx * a.sG;
   const float *T = a.T + (size_t)bidx * a.sT;
@@ -425,7 +252,6 @@ __global__ __launch_bounds__(256, FE_WG_OCC) void wgrad_tn_kernel(WgTable tab) {
   long m1 = m0 + a.rows_per_wg;
   if (m1 > a.M) m1 = a.M;
   if (threadIdx.x < H) redb[threadIdx.x] = 0.f;
-  float *gt = smem + (w * 2 + 0) * 16 * WTS, *tt = smem + (w * 2 + 1) * 16 * WTS;
   f32x4 acc[4][4];
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -433,45 +259,13 @@ __global__ __launch_bounds__(256, FE_WG_OCC) void wgrad_tn_kernel(WgTable tab) {
 #pragma unroll
     for (int tk = 0; tk < 4; ++tk) acc[ti][tk] = f32x4{0.f, 0.f, 0.f, 0.f};
   const bool want_bias = a.db != nullptr;
-#if defined(FE_WG_STAGED)
-  wg_accumulate(G, T, a.ldg, a.ldt, m0 + 16 * w, m1, 64, want_bias, a.round != 0, gt, tt, acc, bsum);
-#elif defined(FE_WG_F32)
-  (void)gt; (void)tt;
-  wg_accumulate_direct(G, T, a.ldg, a.ldt, m0 + 16 * w, m1, 64, want_bias, a.round != 0, acc, bsum);
-#else
-  (void)gt; (void)tt;
   if (a.round) wg_accumulate_x3<true>(G, T, a.ldg, a.ldt, m0 + 32 * w, m1, 128, want_bias, acc, bsum);
   else wg_accumulate_x3<false>(G, T, a.ldg, a.ldt, m0 + 32 * w, m1, 128, want_bias, acc, bsum);
-#endif
-#if defined(FE_WG_STAGED) || defined(FE_WG_ATOMIC_EPILOGUE)
-  __syncthreads();   // all waves are done with their staging tiles
-  for (int k = threadIdx.x; k < IMG; k += 256) red[k] = 0.f;
-  __syncthreads();
-#pragma unroll
-  for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-    for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) atomicAdd(&red[(16 * ti + 4 * q + r) * H + 16 * tk + i], acc[ti][tk][r]);
-#pragma unroll
-  for (int ti = 0; ti < 4; ++ti) {
-    float s = qsum(bsum[ti]);
-    if (q == 0) atomicAdd(&redb[16 * ti + i], s);
-  }
-  __syncthreads();
-  // slab order: [job slabs][batch][split] so that the reducer walks splits contiguously
-  const size_t sidx = (size_t)a.slab_begin + (size_t)bidx * a.nsplit + split;
-  f32x4 *dst = reinterpret_cast<f32x4 *>(tab.slab + sidx * IMG);
-  const f32x4 *src = reinterpret_cast<const f32x4 *>(red);
-  for (int k = threadIdx.x; k < IMG / 4; k += 256) dst[k] = src[k];
-  if (threadIdx.x < H) tab.slab_b[sidx * H + threadIdx.x] = redb[threadIdx.x];
-#else
   // The four waves' 64x64 partials are added in a FIXED order (wave 0 + 1 + 2 + 3): every wave parks its accumulator in
   // LDS in register order (sixteen 16-byte stores per lane, conflict-free), then thread t sums fragment tiles 4 (t / 64) ..
   // + 3 of lane t % 64 and stores them into the slab.  (Until late round 3 every lane added its 256 values to one shared
   // tile with LDS float atomics -- 1 024 64-lane atomics per workgroup, a third of the kernel's wave time by the counters,
   // and an order-dependent sum.)
-  (void)red;
   f32x4 *part = reinterpret_cast<f32x4 *>(smem) + (size_t)w * (IMG / 4);
 #pragma unroll
   for (int ti = 0; ti < 4; ++ti)
@@ -495,7 +289,6 @@ __global__ __launch_bounds__(256, FE_WG_OCC) void wgrad_tn_kernel(WgTable tab) {
     for (int r = 0; r < 4; ++r) dst[(16 * ti + 4 * q + r) * H + 16 * tk + i] = v[r];
   }
   if (threadIdx.x < H) tab.slab_b[sidx * H + threadIdx.x] = redb[threadIdx.x];
-#endif
 }
 
 // Sum the partial slabs of every (job, batch) and accumulate into the gradients.  A workgroup owns

@@ -109,9 +109,9 @@ __device__ __forceinline__ void gemm_i(const void *img, int i, const Vec &in, Ve
 }
 // The products of virt_tile_forward are issued at wave priority 3 (0 elsewhere): of the two waves of a SIMD the one that has
 // matrix work gets the issue port first and the other fills the gaps with its vector work -- virt_fwd 1.64 -> 1.58 ms per
-// step on one box (priority 1: 1.59).  -DVF_PRIO=0 switches it off; -DEF_PRIO=n / -DVB_PRIO=n: the same experiment in the
-// edge kernels / the producers of virt_bwd_pc (measured, not adopted: edge_bwd 3.44 -> 3.61 ms at priority 2, edge_fwd and
-// virt_bwd_pc unchanged at priorities 1 and 2).
+// step on one box (priority 1: 1.59).  -DVF_PRIO=0 switches it off.  The same experiment in the edge kernels / the producers
+// of virt_bwd_pc was measured and not adopted: edge_bwd 3.44 -> 3.61 ms at priority 2, edge_fwd and virt_bwd_pc unchanged at
+// priorities 1 and 2.
 #ifndef VF_PRIO
 #define VF_PRIO 3
 #endif
@@ -125,28 +125,17 @@ __device__ __forceinline__ void gemm_i(const void *img, int i, const Vec &in, Ve
 #ifndef FE_EB_P16   // the software-pipelined f16x2 product in the producers of edge_bwd_pc (common.h); 0 in the three-waves-per-SIMD experiment
 #define FE_EB_P16 1
 #endif
-#ifdef EF_PRIO
-#define EF_PRIO_ON() __builtin_amdgcn_s_setprio(EF_PRIO)
-#define EF_PRIO_OFF() __builtin_amdgcn_s_setprio(0)
-#else
-#define EF_PRIO_ON()
-#define EF_PRIO_OFF()
-#endif
 // the edge stage's four products I = 0 W2, 1 WX1, 2 W2^T, 3 WX1^T: from four split images (RM = false: img + I) or from the
 // two row-major images W2 | WX1 read plain or transposed (RM = true, edge_bwd: half the LDS, which its rings take)
 template <int MODE, int I, bool RM>
 __device__ __forceinline__ void gemm_e(const void *img, const Vec &in, Vec &acc) {
   if constexpr (RM && I >= 2) {   // the transposed products take gradients: the f16x2 form scales them per item
     const auto op = make_grad_operand<MODE>(in);
-    EF_PRIO_ON();
     gemm_rm_g<MODE, true, false, FE_EB_P16 != 0>(static_cast<const char *>(img) + (I & 1) * rm_lds_bytes<MODE>(), op, acc);
-    EF_PRIO_OFF();
   } else {
     const auto op = make_operand<MODE>(in);
-    EF_PRIO_ON();
     if constexpr (RM) gemm_rm<MODE, false, false, FE_EB_P16 != 0>(static_cast<const char *>(img) + (I & 1) * rm_lds_bytes<MODE>(), op, acc);
     else gemm_op<MODE, true>(img, I, op, acc);   // (edge_fwd: the software-pipelined f16x2 product, common.h)
-    EF_PRIO_OFF();
   }
 }
 
@@ -175,13 +164,6 @@ __device__ __forceinline__ void edge_tile_pre(const EdgeArgs &a, const float *ve
   S.rf = (a.flags & FASTEGNN_F_EGNN_NORM) ? (S.r >= 1e-12f ? 1.0f : S.r * 1e12f) : S.r;
 #pragma unroll
   for (int k = 0; k < 8; ++k) S.eav[k] = I.eav[k];
-#ifdef FE_EDGE_PRE_VALU   // rounds 1-3: one vector fma per element and scalar feature
-  static_assert(!FOLD1, "FE_EDGE_PRE_VALU is the unfolded form");
-  vaxpy(pre, S.rf, vload_vec(vec + EV_WR * H, q));
-#pragma unroll
-  for (int k = 0; k < 8; ++k)
-    if (k < a.ea_dim) vaxpy(pre, S.eav[k], vload_vec(vec + (EV_WE + k) * H, q));
-#else
   // The rank-(1 + ea_dim) update pre[o][e] += sum_k Wf[o][k] * feat[k][e], feat = (radial | edge_attr), on the matrix pipe:
   // K = 4 features per v_mfma_f32_16x16x4_f32 (fp32 products, as the vector form).  Lane (q, j) supplies Wf[16t + j][4s + q]
   // as the A operand of block t (rows 4s + q of `vec`: EV_WR = 0, EV_WE + k = 1 + k; rows past the last feature are zero)
@@ -213,7 +195,6 @@ __device__ __forceinline__ void edge_tile_pre(const EdgeArgs &a, const float *ve
       for (int t = 0; t < 4; ++t) pre.t[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[16 * t], f1, pre.t[t], 0, 0, 0);
     }
   }
-#endif
   FE_T(1)   // gathered rows arrived, pre-activation formed
 }
 // part 2: the two 64x64 layers and the coordinate head
@@ -235,10 +216,6 @@ __device__ __forceinline__ void edge_tile_mlp(const EdgeArgs &a, const void *img
   else S.t = KEEP_D ? vsilu_keep_d(pre FE_ACT(a)) : vsilu(pre FE_ACT(a));
   FE_T(2)   // silu 1
   S.mp = vload_vec(vec + EV_B2 * H, q);
-#ifdef FE_EDGE_T2   // diagnostic lever: two-part split of the first chained layer's operand (forward kernel, fp32 mode)
-  if constexpr (!KEEP_D && MODE == GM_X3 && !RM) gemm64_x3_t2(reinterpret_cast<const unsigned *>(img), S.t, S.mp);
-  else
-#endif
   gemm_e<MODE, 0, RM>(img, S.t, S.mp);
   FE_T(3)   // gemm 1
   if constexpr (FOLD) S.m0 = vsilu2(S.mp);
@@ -334,25 +311,12 @@ __device__ __forceinline__ void virt_tile_forward(const VirtArgs &a, const void 
     S.vd[2] = Zb[2 * C + c] - xi[2];
   }
   S.vr = sqrt_f(S.vd[0] * S.vd[0] + S.vd[1] * S.vd[1] + S.vd[2] * S.vd[2]);
-#ifdef FE_VIRT_PRE_MFMA   // measured lever, rejected (round 4: virt_fwd 1.336 -> 1.341 ms per step, tools/gpu_lever_virt_pre_mfma.sh)
-  if (BcL) {
-    // pre = A[n] + Bc[c] + vr * w_vr as ONE rank-2 update on the matrix pipe (as edge_tile_pre): features (vr, 1) of the
-    // node against the columns (w_vr | Bc[c]); lanes q = 0 supply w_vr and vr, lanes q = 1 Bc[c] and 1, the others a zero
-    // feature.  16 adds + 16 fmas + 8 LDS reads per (tile, channel) become 4 MFMAs + 4 LDS words -- and nothing is gained:
-    // this kernel runs two waves per SIMD with its matrix pipe twice as busy as edge_fwd's.
-    const int j = lane_id() & 15;
-    const float *wsrc = (q == 0 ? vec + VV_WVR * H : BcL + c * H) + j;
-    const float f = q == 0 ? S.vr : (q == 1 ? 1.f : 0.f);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) S.pre.t[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wsrc[16 * t], f, Ai.t[t], 0, 0, 0);
-  } else
-#endif
-  {
-    S.pre = Ai;
-    if (BcL) vadd(S.pre, vload_vec(BcL + c * H, q));
-    else vadd(S.pre, vload_row(a.Bc + ((size_t)b * C + c) * H, q));
-    vaxpy(S.pre, S.vr, vload_vec(vec + VV_WVR * H, q));
-  }
+  // pre = A[n] + Bc[c] + vr * w_vr on the vector ALU.  (As ONE rank-2 update on the matrix pipe, as edge_tile_pre, nothing is gained:
+  // round 4, virt_fwd 1.336 -> 1.341 ms per step -- this kernel runs two waves per SIMD with its matrix pipe twice as busy as edge_fwd's.)
+  S.pre = Ai;
+  if (BcL) vadd(S.pre, vload_vec(BcL + c * H, q));
+  else vadd(S.pre, vload_row(a.Bc + ((size_t)b * C + c) * H, q));
+  vaxpy(S.pre, S.vr, vload_vec(vec + VV_WVR * H, q));
   S.t = vsilu(S.pre FE_ACT(a));
   VF_T(1)   // geometry, pre-activation, silu 1
   S.vp = vload_vec(vec + VV_C2 * H, q);

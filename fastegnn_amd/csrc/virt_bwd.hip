@@ -186,15 +186,7 @@ __global__ __launch_bounds__(64 * VB_GV_WAVES) void virt_bwd_gv_kernel(VirtGvArg
     for (int k = 0; k < ncv; ++k) {
       Vec acc = vload_row(pv + (size_t)k * H, q);
       gemm_rm<SM, true>(img + k * RM_BYTES, op, acc);
-#ifdef VB_GV_NT   // measured lever, rejected: non-temporal stores for the Gv rows (0.49 -> 1.39 ms per step)
-      if (valid) {
-        float *row = a.Gv + (size_t)(c0 + k) * a.cstride + (size_t)n * H;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) __builtin_nontemporal_store(acc.t[t], reinterpret_cast<f32x4 *>(row + 16 * t + 4 * q));
-      }
-#else
-      if (valid) vstore_row(a.Gv + (size_t)(c0 + k) * a.cstride + (size_t)n * H, q, acc);
-#endif
+      if (valid) vstore_row(a.Gv + (size_t)(c0 + k) * a.cstride + (size_t)n * H, q, acc);   // (non-temporal stores, measured: 0.49 -> 1.39 ms per step)
     }
   }
 }
@@ -266,10 +258,6 @@ __device__ __forceinline__ void vb_tile_store(float *tile, int j, int q, const V
 }
 // row[o] += sum over the 16 items of the tile of u[o][item]: transposing DPP butterfly, then ONE 64-lane atomic
 __device__ __forceinline__ void vb_accum_items(float *row, const Vec &u, int j, int q) {
-#ifdef VB_DIAG_NOACC   // diagnostic: what do the DPP sums + LDS atomics of the rank-1 gradients and pools cost?
-  if (u.t[0][0] == 12345.678f) row[0] = 1.f;
-  return;
-#endif
   tile_sum_add(row, u, j, q);
 }
 
@@ -309,11 +297,7 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
   const int t_lo = (int)((long)blockIdx.x * ntiles / gridDim.x), t_hi = (int)((long)(blockIdx.x + 1) * ntiles / gridDim.x);
   const int n_fine = min(t_hi - t_lo, VB_FINE_TILES), n_coarse = t_hi - t_lo - n_fine;
   const int n_units = n_coarse + n_fine * A.NGF;
-#ifdef VB_DIAG_NOPUB   // diagnostic: producers skip the ring hand-offs, consumers have nothing to do
-  const int total = 0;
-#else
   const int total = (t_hi - t_lo) * C;            // (tile, channel) operand sets = tickets per ring
-#endif
   const int cur = a.batch[t_lo * 16];             // graph whose pools this workgroup accumulates in LDS
   const bool tanh_on = a.flags & FASTEGNN_F_TANH;
 
@@ -434,11 +418,7 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
     finish(acc0, sG0, role0, bs0);
     if (two_acc) finish(acc1, sG1, 1, bs1);
     }
-#ifdef VB_NO_CONS
-  } else if (false) {
-#else
   } else if (consumer) {
-#endif
     // ---------------------------------------------------------------------------------------------------------
     // consumers (as in edge_bwd_pc_kernel): one 64x64 accumulator each, two tickets of the ring per step (K = 32 rows),
     // operands split into bf16 parts here, six bf16x3 products per 16x16 tile (one in bf16 mode); the slots are handed
@@ -592,11 +572,7 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
       s0 += __shfl_xor(s0, 32);
       if (q == 0) A.slab_b[sl * H + 16 * ti + j] = (float)s0;
     }
-#ifdef VB_NO_PROD
-  } else if (false) {
-#else
   } else {
-#endif
     // ---------------------------------------------------------------------------------------------------------
     // producers: forward recompute of (tile, channel) interleaved with its adjoint.  Register budget: 256 per wave
     // (two waves per SIMD), so the channel-invariant rows are re-read per channel (L2), the tile's g_A accumulates
@@ -606,20 +582,11 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
     const float invC = 1.0f / (float)C;
     const float attb0 = ATT ? a.attb[0] : 0.f;
     float *racc = racc0 + ((wv > 3 ? wv - 1 : wv) % A.nbank) * VB_RACC;   // this producer's bank (producers: waves 0,1,2,4,5)
-#ifdef VB_PRIO
-#define VB_PRIO_ON() __builtin_amdgcn_s_setprio(VB_PRIO)
-#define VB_PRIO_OFF() __builtin_amdgcn_s_setprio(0)
-#else
-#define VB_PRIO_ON()
-#define VB_PRIO_OFF()
-#endif
     // (P16 = false: this kernel sits at 256 registers with spills; the pipelined f16x2 product costs it more than it hides, common.h)
-    auto mm = [&](int which, const SOp &op, Vec &acc) { VB_PRIO_ON(); gemm_rm<SM, false, true, false>(rmimg + which * RMS, op, acc); VB_PRIO_OFF(); };
+    auto mm = [&](int which, const SOp &op, Vec &acc) { gemm_rm<SM, false, true, false>(rmimg + which * RMS, op, acc); };
     auto mmT = [&](int which, const Vec &g, Vec &acc) {
       const auto op = make_grad_operand<SM>(g);   // (the f16x2 form scales a gradient per item)
-      VB_PRIO_ON();
       gemm_rm_g<SM, true, true, false>(rmimg + which * RMS, op, acc);
-      VB_PRIO_OFF();
     };
     VB2_T0()
     for (;;) {
@@ -661,10 +628,8 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
       const unsigned offA = grp == 0 ? offN : (unsigned)j * H + 4u * q;
       // the tile's g_A stays in 16 registers across the channels of the unit and is stored once (round 4; round 3 accumulated it
       // through memory per channel: with the bf16x3 operands there was no room -- now 9 spilled registers, virt_bwd 3.21 -> 3.10 ms
-      // per step, 1.30 -> 1.11 GB of HBM traffic per launch; -DVB_GA_MEM restores the old form)
-#ifndef VB_GA_MEM
+      // per step, 1.30 -> 1.11 GB of HBM traffic per launch)
       Vec ga_acc = vzero();
-#endif
 #pragma unroll 1
       for (int c = c_lo; c < c_hi; ++c) {
         asm volatile("" ::: "memory");
@@ -734,7 +699,6 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
         // v[c][n] takes the place of Gv[c][n]: ONE [C][N][64] array serves both (the row has just been requested by this
         // very lane; same-address accesses of a lane stay in program order)
         if (valid) vstore_u(A.wg_v + cb, offN, v);
-#ifndef VB_DIAG_NOPUB
         {   // (g_ux, v) and (g_uX, v) to consumers X and XX: one slot of ring A, free once both have drained it
           int tk = 0;
           if (l == 0) tk = atomicAdd(&ctrl[VBC_HEAD + 0], 1);
@@ -750,7 +714,6 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");   // lgkmcnt(0): the tiles are in LDS before the flag
           if (l == 0) vb_st(&ctrl[VBC_FILLED + sl], round + 1);
         }
-#endif
         VB2_T(6)   // publish to ring A
         g_v = vb_mask(g_v, valid);
         mmT(1, g_ux, g_v);
@@ -770,12 +733,8 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
           vaxpy(g_v0, g_z, vload_vec(vec + VV_ATT * H, q));
         }
         Vec g_t = vzero();
-#ifdef VB_GA_MEM
-        Vec ga = vzero();
-#endif
         {
           const Vec g_vp = vmul(g_v0, vp);
-#ifndef VB_DIAG_NOPUB
           {   // (g_vp, t) to consumer V2
             int tk = 0;
             if (l == 0) tk = atomicAdd(&ctrl[VBC_HEAD + 1], 1);
@@ -789,23 +748,13 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
             if (l == 0) vb_st(&ctrl[VBC_FILLED + VB_MAXRING + sl], round + 1);
           }
-#endif
           VB2_T(8)   // g_vp + publish to ring B
-          // requested here, consumed after the product: the tile's running g_A
-#ifdef VB_GA_MEM
-          if (c > c_lo) ga = vload_u(dA, offA);
-#endif
           mmT(0, g_vp, g_t);
         }
         VB2_T(9)   // V2^T product
         const Vec g_pre = vmul(g_t, d_pre);
-#ifndef VB_GA_MEM
         vadd(ga_acc, g_pre);
         if (c + 1 == c_hi && valid) vstore_u(dA, offA, ga_acc);
-#else
-        vadd(ga, g_pre);   // g_A of the tile accumulates through memory (the same lane re-reads its own row)
-        if (valid) vstore_u(dA, offA, ga);
-#endif
         vb_accum_items(racc + 2 * H, vscale(g_pre, vr), j, q);
         const float g_vr = vdot(g_pre, vload_vec(vec + VV_WVR * H, q));
         const float ivr = vr > 0.f ? g_vr * rcp_f(vr) : 0.f;
@@ -1180,11 +1129,7 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
       bool w_have[2] = {false, false};             // the parity's scratch tile holds a partial sum
       int since_w = 0;
       int *drainedA = ctrl + VBSC_DRAINED + VB_MAXRING, *drainedB = ctrl + VBSC_DRAINED + 2 * VB_MAXRING;
-#ifdef FE_VBS_SWAP   // measured alternative: the light (g_vp, t) contraction beside producer 2 on SIMD 2, (g_np, v) beside wave 3 on SIMD 3
-      const bool doV2n = FIVEP ? wv == VB_CONS_V2 : wv == VB_CONS_XX, doWn = wv == VB_CONS_XX;
-#else
       const bool doV2n = wv == VB_CONS_XX, doWn = FIVEP ? wv == VB_CONS_V2 : wv == VB_CONS_XX;
-#endif
       const bool doV2 = NODE ? doV2n : true, doW = NODE && doWn;   // (NODE = false: wave 7 is the only wave here, and ring B its only ring)
       // acc (+ the parity's scratch tile) -> the channel's running sum over the blocks, ACCUMULATOR order, plain read-modify-write
       // (the slab is this wave's own; the reduction kernel reads that order: WgJob::acc32)
@@ -1264,12 +1209,10 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
               w_par = par;
               since_w = 0;
             }
-#ifndef VBS_DIAG_NO_W   // diagnostic: wave 7 only drains its ring-A tickets (results are wrong without the contraction)
             const float f = sGw.update_lazy(xg) * sTw.update_lazy(xt);
             if (f != 1.f) wg32_scale_acc(acc1, f);
             const WgOp32 G = wg32_split(xg, sGw.scale()), T = wg32_split(xt, sTw.scale());
             wg32_mma(acc1, G, T);
-#endif
             ++doneA;
             if (++w_cnt[par] == nb_ph) {               // the phase is complete: into the channel's running sum of this workgroup
               flush_w(acc1, sGw.inv(), sTw.inv(), 3 + par, w_have[par], A.w_slab + ((size_t)ch * gridDim.x + blockIdx.x) * IMG, first_blk != 0);

@@ -16,7 +16,7 @@ constexpr int VIRT_FWD_IMG_FLOATS = 5 * IMG3;
 constexpr int VIRT_FWD_PAIR_STAGE = 4 * 4096;
 constexpr int VIRT_FWD_IMG_FLOATS_PAIR = 3 * IMG3 + VIRT_FWD_PAIR_STAGE;
 inline size_t virt_fwd_lds_bytes(int C, bool pair = false) {
-  return (size_t)((pair ? VIRT_FWD_IMG_FLOATS_PAIR : VIRT_FWD_IMG_FLOATS) + VV_COUNT * H + 2 * (C * H + ((3 * C + 3) & ~3)) + 4) * sizeof(float);   // + 4 control words
+  return (size_t)((pair ? VIRT_FWD_IMG_FLOATS_PAIR : VIRT_FWD_IMG_FLOATS) + VV_COUNT * H + 2 * (C * H + ((3 * C + 3) & ~3)) + 4) * sizeof(float);   // + 4 words nothing reads any more (kept: the launch is unchanged)
 }
 // NODE = false: the node update of this layer is not wanted (h_out == NULL && HvT_out == NULL in the layer descriptor: nothing reads h / Hv
 // after the last layer of FastEGNN) -- no W3c stage, no node_mlp.0 accumulation, no node-MLP tail, no npre / h_out stores, no poolV sums;
@@ -34,21 +34,6 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
   float *poolX_l = poolV_l + C * H;              // [3][C]
   float *Bc_l = poolX_l + ((3 * C + 3) & ~3);    // [C][64]: Bc rows of the graph the workgroup is in
   float *Z_l = Bc_l + C * H;                     // [3][C]: its virtual coordinates
-#ifdef VF_SPLIT_BARRIER
-  // measured alternative to the per-channel workgroup barrier: per stage slot a count of committed image shares and a count
-  // of waves that are done with the image (monotonic; a wave waits only for what it needs, at most one channel of skew)
-  int *ctl = reinterpret_cast<int *>(Z_l + ((3 * C + 3) & ~3));   // filled[2] | done[2]
-  if (threadIdx.x < 4) ctl[threadIdx.x] = 0;
-  int vf_steps = 0;   // staged steps this workgroup has completed (the same in every wave)
-  auto vf_signal = [&](int k) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane_id() == 0) atomicAdd(&ctl[k], 1);
-  };
-  auto vf_wait = [&](int k, int need) {
-    while (__atomic_load_n(&ctl[k], __ATOMIC_RELAXED) < need) __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  };
-#endif
   load_images_x3(reinterpret_cast<unsigned *>(img), wpack_x3(a.wpack, C, I_V2), 3);
   virt_load_vecs(vec, a);
   for (int i = threadIdx.x; i < C * H + 3 * C; i += blockDim.x) poolV_l[i] = 0.f;
@@ -150,9 +135,6 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
     if (staged) {
       __syncthreads();            // every wave is done with the stage (the previous step's node-level images)
       commit_w3c(0);
-#ifdef VF_SPLIT_BARRIER
-      vf_signal(0);
-#endif
       if ((PAIR ? (C + 1) / 2 : C) > 1) fetch_w3c(1);
     }
     // iterations of the channel walk: C (a wave per tile), ceil(C / 2) (PAIR), this wave's share of C (a left-over tile dealt by channel)
@@ -161,20 +143,6 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
     for (int it = 0; it < n_it; ++it) {
       const int c = PAIR ? 2 * it + grp : (split ? wv + it * VIRT_WAVES : it);
       const bool chan = !PAIR || c < C;          // (PAIR, odd C: the second wave sits out the last iteration)
-#if defined(VF_SPLIT_BARRIER)
-      static_assert(!PAIR, "VF_SPLIT_BARRIER is a lever of the one-wave-per-tile walk");
-      if (staged) {
-        const int sl = c & 1, s1 = sl ^ 1, per0 = (C + 1) >> 1, per1 = C >> 1;
-        if (c + 1 < C) {
-          // every wave is done with channel c - 1 (the previous image of slot s1) ...
-          vf_wait(2 + s1, VIRT_WAVES * (vf_steps * (s1 ? per1 : per0) + ((c + 2 - s1) >> 1)));
-          commit_w3c(s1);           // ... this wave's share of W3c[c + 1]
-          vf_signal(s1);
-          if (c + 2 < C) fetch_w3c(c + 2);
-        }
-        vf_wait(sl, VIRT_WAVES * (vf_steps * (sl ? per1 : per0) + (c >> 1) + 1));   // every share of W3c[c] is in slot c & 1
-      }
-#elif !defined(VF_DIAG_NOSTAGE)   // diagnostic: what do the per-channel stage refill and its barrier cost? (results are wrong without them)
       if (staged) {
         __syncthreads();          // W3c[c] is in slot c & 1; every wave is done with channel c - 1, i.e. with the other slot
         if (it + 1 < n_it) {
@@ -182,7 +150,6 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
           if (it + 2 < n_it) fetch_w3c(it + 2);
         }
       }
-#endif
       VF_T(0)   // per-channel barrier + stage refill
       if (active && chan) {
         VirtFwdState<MODE> S;
@@ -210,25 +177,13 @@ __global__ __launch_bounds__(64 * VIRT_WAVES) void virt_fwd_kernel(VirtArgs a) {
         }
         VF_T(6)   // pools
         if (!rf) {
-#ifdef VF_DIAG_NODE_IMG0      // diagnostic: the node-MLP block product from a resident image instead of the stage (wrong results)
-          gemm_op<MODE>(img, 0, S.vs, nodeacc);
-#elif defined(VF_DIAG_NONODE)  // diagnostic: no node-MLP block product (wrong results)
-          if (S.vs.p[0][0][0] == 0x12345678u) nodeacc = S.v;
-#else
           if (split) gemm_op<MODE>(wpack_x3(a.wpack, C, img_w3c(c)), 0, S.vs, nodeacc);   // the stage serves the stepped walk only
           else if constexpr (PAIR) gemm64_f2<false>(stage, S.vs, nodeacc, (2 * (it & 1) + (int)(threadIdx.x >> 8)) * 1024);   // slot 2 (it & 1) + grp: 4 096 words each
           else gemm_op<MODE>(stage + (c & 1) * IMG3, 0, S.vs, nodeacc);
-#endif
         }
         VF_T(7)   // node-MLP block product
       }
-#ifdef VF_SPLIT_BARRIER
-      if (staged) vf_signal(2 + (c & 1));   // this wave is done with the image of channel c
-#endif
     }
-#ifdef VF_SPLIT_BARRIER
-    if (staged) ++vf_steps;
-#endif
     if constexpr (PAIR) {   // the second wave's share of the tile's node-MLP accumulator and coordinate update -> the first wave
       float *comb = lds + 3 * IMG3;      // (the stage, as floats: four [16][TS] tiles)
       const int co = ((wv & 3) * 16 + j) * TS;
