@@ -182,6 +182,23 @@ GRAD_EXCEPTIONS = [
      "activations other than SiLU at 4 000 nodes: bias gradients are column sums over 32 k - 48 k rows behind erf / exp / "
      "log1p evaluations of 2-4 ulp; measured 4.64e-6 against 2 x ref + 1e-6 = 2.96e-6 (act_mid_gelu, "
      "gcl_1.edge_mlp_virtual.0.bias)"),
+    # The wide-range build (libfastegnn_hip_x3.so: tests/test_gpu_x3_build.py runs the comparisons of the f16x2 build under their case names).  Over the
+    # 2 780 comparisons the two builds share (1 654 of them above 3e-7), the median ratio of their distances to fp64 is 1.00 (bf16x3 further by more than
+    # 1.5 x on 264 tensors, f16x2 on 258; up to 5 x either way on single cancelling sums): equally accurate, other draws -- virt_fwd_kernel runs one wave per tile where
+    # the f16x2 build adds two partial sums, and a product is six bf16 partial products added smallest first instead of hh + (hl + lh) / 2^11.  Two
+    # comparisons land beyond the plain rule on this build; each floor is 1.5 x the largest measured excess over 2 x ref
+    (r"^test_c48$", r"^gcl_0\.node_mlp_virtual\.0\.bias$", 2.0, 3.0e-6,
+     "bf16x3 build, C = 48 (700 + 333 nodes): the column sum of 96 (graph, channel) rows behind the whole layer-1 backward and the pools of 65 "
+     "single-tile workgroups, whose fp32 atomics arrive in another order every run; the sum cancels (the reference's fp32 draw: 2.87e-6 .. 2.91e-6 on the "
+     "GPU box's host, 4.0e-6 .. 4.1e-6 on another host; oracle/factored.py's re-association in fp32 on the CPU 2.4e-6 .. 2.7e-6).  Eleven runs on one box: "
+     "5.69e-6 5.88e-6 5.93e-6 6.11e-6 6.23e-6 6.72e-6 6.81e-6 6.91e-6 7.08e-6 7.29e-6 7.75e-6 against 2 x ref + 1e-6 = 6.75e-6 .. 6.82e-6; the f16x2 "
+     "build, five runs: 2.48e-6 .. 2.90e-6.  On six other seeds of the shape no tensor of either build passes 0.5 of its tolerance (geometric mean of "
+     "bf16x3 / f16x2 over all tensors: 1.13)"),
+    (r"^test_no_edges_and_isolated_nodes$", r"^gcl_1\.edge_mlp_virtual\.2\.bias$", 2.0, 3.9e-6,
+     "bf16x3 build, the empty edge set (63 nodes, C = 4): a column sum over N * C = 252 rows that cancels (reference 1.79e-6 on the GPU box's host, "
+     "2.16e-6 .. 2.36e-6 on another; the CPU re-association 1.94e-6).  Seven runs on one box take three values -- 4.29e-6 (3 x), 5.05e-6 (3 x), 6.18e-6 "
+     "(once): the order in which the pools' atomics of four workgroups arrive -- against 2 x ref + 1e-6 = 4.58e-6; the f16x2 build 1.21e-6.  The row the "
+     "bf16x3 build had here while it was the default (rounds 1-3: floor 2e-6 at a measured 4.67e-6) left with it in round 4"),
 ]
 
 

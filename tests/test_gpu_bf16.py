@@ -180,6 +180,68 @@ def test_bf16_cfg3_shape_backward_vs_mirror():
     assert not bad, bad
 
 
+@pytest.mark.parametrize("C", [32, 64])
+def test_bf16_more_than_16_channels_vs_mirror(C):
+    """bf16 operands at C >= 32: the producer / consumer virtual backward then keeps 3 + 2 ring slots beside its three 27 648-byte images
+    (csrc/virt_bwd.hip; 4 + 2 up to C = 16, which is all the other cases of this file reach), with three accumulator banks at C = 64.  Two ragged
+    graphs of 700 and 333 nodes (65 tiles: the rings wrap many times), two layers, gravity, trained-like coordinate heads; outputs, every
+    parameter gradient and the input gradients against the mode's mirror in fp32 and fp64 under the constants of this file.  Only the last
+    layer's unread heads (node_mlp / node_mlp_virtual: exact zeros in the mirror) are left out of the gradient comparison."""
+    from tests.test_gpu_properties import _batch
+    inp = _batch([700, 333], 9, C, seed=60 + C)
+    batch = {k: v.cuda() for k, v in inp.items()}
+    target = batch["node_loc"] + 0.5
+    torch.manual_seed(3)
+    m = fastegnn_amd.FastEGNN(2, 0, 2, 64, C, device="cuda", n_layers=2, gravity=[0, -1, 0], mlp_dtype=torch.bfloat16)
+    with torch.no_grad():
+        for k, p in m.named_parameters():
+            if k.endswith(("coord_mlp_r.2.weight", "coord_mlp_r_virtual.2.weight", "coord_mlp_v_virtual.2.weight")):
+                p.mul_(50.0)          # trained-like coordinate heads: the coordinate paths carry gradient
+    leaf = {k: batch[k].clone().requires_grad_(True) for k in ("node_feat", "node_loc", "node_vel", "loc_mean")}
+    loc, vloc = m(**dict(batch, **leaf))
+    wv = torch.linspace(-1.0, 1.0, vloc.numel(), device="cuda").view_as(vloc)
+    golden_loss(loc, vloc, target, wv).backward()
+    G = {k: (p.grad.cpu() if p.grad is not None else torch.zeros_like(p).cpu()) for k, p in m.named_parameters()}
+    gin = {k: v.grad.cpu() for k, v in leaf.items()}
+    cfg = R.Config(2, 0, 2, 64, C, n_layers=2, gravity=[0, -1, 0], bf16=True)
+
+    def mirror(dt):
+        p = {k: v.detach().cpu().to(dt) for k, v in m.state_dict().items()}
+        kw = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in inp.items()}
+        lo, vl, ctx = F.model_forward(p, cfg, **kw)
+        l2, v2 = lo.clone().requires_grad_(True), vl.clone().requires_grad_(True)
+        golden_loss(l2, v2, target.cpu().to(dt), wv.cpu().to(dt)).backward()
+        Gm, gim = F.model_backward(p, cfg, ctx, l2.grad, v2.grad)
+        return lo, vl, Gm, gim
+
+    l32, v32, G32, gin32 = mirror(torch.float32)
+    l64, v64, G64, gin64 = mirror(torch.float64)
+    x0 = inp["node_loc"].double()
+    assert (l64 - x0).abs().max().item() > 1e-2                # the coordinate path is exercised
+    bad = []
+    for k, got, ref in (("loc", loc, l32), ("vloc", vloc, v32)):
+        print(f"bf16 C={C} {k} vs mirror32 {rel_err(got, ref):.2e}")
+        if rel_err(got, ref) > OUT_VS_MIRROR:
+            bad.append((k + " vs mirror", rel_err(got, ref)))
+    assert set(G64) == set(G) and set(gin64) == set(gin)
+    pairs = [("displacement", loc.detach().cpu().double() - x0, l32.double() - x0, l64 - x0)]
+    pairs += [(k, G[k], G32[k], G64[k]) for k in G64]
+    pairs += [("gin/" + k, gin[k], gin32[k], gin64[k]) for k in gin64]
+    skipped = []
+    for k, got, m32, m64 in pairs:
+        if float(m64.abs().max()) == 0.0:
+            assert float(got.abs().max()) == 0.0, k
+            skipped.append(k)
+            continue
+        e_got, e_ref = rel_err(got, m64), rel_err(m32, m64)
+        print(f"bf16 C={C} {k} {e_got:.2e} mirror32 {e_ref:.2e} tol {GRAD_FACTOR * e_ref + GRAD_FLOOR:.2e}")
+        if e_got > GRAD_FACTOR * e_ref + GRAD_FLOOR:
+            bad.append((k, f"{e_got:.2e}", f"mirror32 {e_ref:.2e}"))
+    unread = {f"gcl_1.{n}.{i}.{w}" for n in ("node_mlp", "node_mlp_virtual") for i in (0, 2) for w in ("weight", "bias")}
+    assert set(skipped) <= unread, skipped
+    assert not bad, bad
+
+
 def test_bf16_flag_changes_the_arithmetic_and_fp32_default_does_not():
     """Guards against a silently ignored flag: on the same weights the bf16 mode differs from the fp32 mode by the
     expected 1e-4..1e-2 of the displacement, not by 0 and not by more."""

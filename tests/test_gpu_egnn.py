@@ -11,15 +11,21 @@ from tests.test_egnn_oracle_cpu import EGNN_NAMES, EGNN_WIDE_NAMES, egnn_act, eg
 pytestmark = pytest.mark.gpu
 
 
+def _egnn_of_golden(g):
+    """the module a golden's meta describes, before its weights are loaded (a helper of its own: tests/test_gpu_x3_build.py wraps it to run
+    the same comparison on the wide-range build)"""
+    meta = g["meta"]
+    return fastegnn_amd.EGNN(n_layers=int(meta["L"]), in_node_nf=2, in_edge_nf=2, hidden_nf=int(meta.get("hidden", 64)), device="cuda",
+                             with_v=bool(int(meta["with_v"])), norm=bool(int(meta.get("norm", 0))), flat=bool(int(meta.get("flat", 0))))
+
+
 # (EGNN_WIDE_NAMES: flat=True and hidden_nf = 128 -- the sibling on the unfused wide path, fastegnn_amd/wide.py)
 @pytest.mark.parametrize("name", EGNN_NAMES + EGNN_WIDE_NAMES)
 def test_egnn_matches_reference_golden(name):
     g = load_egnn(name)
     with_v = bool(int(g["meta"]["with_v"]))
     norm = bool(int(g["meta"].get("norm", 0)))
-    hidden, flat = int(g["meta"].get("hidden", 64)), bool(int(g["meta"].get("flat", 0)))
-    m = fastegnn_amd.EGNN(n_layers=int(g["meta"]["L"]), in_node_nf=2, in_edge_nf=2, hidden_nf=hidden, device="cuda", with_v=with_v,
-                          norm=norm, flat=flat)
+    m = _egnn_of_golden(g)
     assert m._wide == (name in EGNN_WIDE_NAMES)
     assert list(m.state_dict().keys()) == list(g["p"].keys())
     m.load_state_dict(g["p"], strict=True)
