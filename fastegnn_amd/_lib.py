@@ -176,6 +176,8 @@ def lib(act: bool = False, wide=None):
     # the device-side MMD sample and the ragged loss: additive as well
     L.fastegnn_mmd_sample.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]
     L.fastegnn_loss_mse_mmd_ragged.argtypes = [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp, _vp]
+    # the forward-only loss with its running sums on the device: additive
+    L.fastegnn_loss_mse_mmd_eval.argtypes = [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp]
     L.fastegnn_radius_graph_ws_bytes.restype = C.c_size_t
     L.fastegnn_radius_graph_ws_bytes.argtypes = [_i32]
     L.fastegnn_radius_graph_count.argtypes = [_vp, _i32, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]
@@ -273,7 +275,7 @@ EXPORTED = STAGE_FUNCS + [
     "fastegnn_layer_forward", "fastegnn_layer_backward", "fastegnn_selftest_gemm", "fastegnn_selftest_rm", "fastegnn_selftest_jreduce", "fastegnn_selftest_lane_sums", "fastegnn_selftest_wgrad", "fastegnn_selftest_wgrad_plan", "fastegnn_selftest_wgrad_guard", "fastegnn_selftest_stream", "fastegnn_selftest_chain", "fastegnn_selftest_chain_bf3",
     "fastegnn_augment_edge_attr", "fastegnn_loss_mse_mmd", "fastegnn_adam_step", "fastegnn_adam_step_v2",
     "fastegnn_grad_sqnorm_partials", "fastegnn_grad_sqnorm", "fastegnn_adam_dev_scratch_bytes", "fastegnn_adam_step_dev",
-    "fastegnn_mmd_sample", "fastegnn_loss_mse_mmd_ragged",
+    "fastegnn_mmd_sample", "fastegnn_loss_mse_mmd_ragged", "fastegnn_loss_mse_mmd_eval",
     "fastegnn_radius_graph_ws_bytes", "fastegnn_radius_graph_count", "fastegnn_radius_graph_fill",
     "fastegnn_cutoff_tmp_bytes", "fastegnn_cutoff_edges", "fastegnn_nbody_cutoff_edges",
     "fastegnn_profile_enable", "fastegnn_profile_kernels", "fastegnn_profile_name", "fastegnn_profile_collect",

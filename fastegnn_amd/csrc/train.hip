@@ -236,6 +236,85 @@ __global__ __launch_bounds__(256) void grad_sqnorm_final_kernel(const double *pa
   if (threadIdx.x == 0) *out = s;
 }
 
+// ---- the loss of a forward-only epoch (fastegnn_loss_mse_mmd_eval): MSE and MSE + MMD of one batch, no gradients, added into three
+// fp64 words on the device.  The entry point has no workspace argument, so the two-stage scheme above collapses to its second stage:
+// ONE workgroup of 16 waves takes every sum in a fixed order (thread i owns elements i, i + 1024, ...; xor butterfly within a wave;
+// the 16 wave sums in ascending order) -- no atomics, bit-identical from run to run.  It streams 24 bytes per node with 16-byte
+// loads; the MMD part walks the graphs one after the other with the rows of the graph in LDS, as loss_mmd_kernel holds them.
+constexpr int EVAL_THREADS = 1024;
+__device__ inline double eval_block_sum(double s, double *red) {
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  __syncthreads();   // (the slots of an earlier sum have been read by everyone)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  double t = 0.0;
+  for (int w = 0; w < EVAL_THREADS / 64; ++w) t += red[w];
+  return t;   // the same value in every thread
+}
+__global__ __launch_bounds__(EVAL_THREADS) void loss_eval_kernel(const float *pred, const float *tgt, const float *vloc,
+                                                                 const int32_t *samp, const int32_t *cnt, long n3, int B, int C, int S,
+                                                                 float sigma, float weight, double *acc) {
+  extern __shared__ float sm[];
+  __shared__ double red[EVAL_THREADS / 64];
+  float *V = sm;           // [C][3]
+  float *R = sm + 3 * C;   // [S][3]
+  // MSE: the difference and its square are exact in fp64
+  double s = 0.0;
+  long done = 0;
+  if (((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(tgt)) & 15) == 0) {   // 16-byte loads over the aligned body, scalar tail
+    const long n4 = n3 / 4;
+    const f32x4 *p4 = reinterpret_cast<const f32x4 *>(pred), *t4 = reinterpret_cast<const f32x4 *>(tgt);
+    for (long i = threadIdx.x; i < n4; i += EVAL_THREADS) {
+      const f32x4 x = p4[i], y = t4[i];
+      for (int k = 0; k < 4; ++k) {
+        const double d = (double)x[k] - (double)y[k];
+        s += d * d;
+      }
+    }
+    done = 4 * n4;
+  }
+  for (long i = done + threadIdx.x; i < n3; i += EVAL_THREADS) {
+    const double d = (double)pred[i] - (double)tgt[i];
+    s += d * d;
+  }
+  const double mse = eval_block_sum(s, red) / (double)n3;
+  // MMD (samp null: not wanted): the kernel values are loss_mmd_kernel's fp32 ones, weighted and summed in fp64
+  double mmd = 0.0;
+  if (samp) {
+    const float i2s = 1.0f / (2.f * sigma * sigma);
+    const double w_vv = (double)weight / ((double)B * C * C), w_rv = -2.0 * (double)weight / ((double)B * S * C);
+    double part = 0.0;
+    for (int b = 0; b < B; ++b) {
+      int Sb = cnt ? cnt[b] : S;
+      Sb = Sb < 0 ? 0 : (Sb > S ? S : Sb);   // as loss_mmd_kernel: the staging below must stay inside the S rows of LDS
+      __syncthreads();                       // the rows of the graph before are done with
+      for (int i = threadIdx.x; i < 3 * C; i += EVAL_THREADS) {
+        const int c = i / 3, k = i % 3;
+        V[i] = vloc[((size_t)b * 3 + k) * C + c];
+      }
+      for (int i = threadIdx.x; i < 3 * Sb; i += EVAL_THREADS) {
+        const int r = i / 3, k = i % 3;
+        R[i] = pred[(size_t)samp[(size_t)b * S + r] * 3 + k];
+      }
+      __syncthreads();
+      for (int i = threadIdx.x; i < C * C + Sb * C; i += EVAL_THREADS) {
+        const bool vv = i < C * C;
+        const int a = vv ? i / C : (i - C * C) / C, c = vv ? i % C : (i - C * C) % C;
+        const float *xa = vv ? V + 3 * a : R + 3 * a;
+        const float d0 = xa[0] - V[3 * c], d1 = xa[1] - V[3 * c + 1], d2 = xa[2] - V[3 * c + 2];
+        const float kv = __expf(-sqrtf(d0 * d0 + d1 * d1 + d2 * d2) * i2s);
+        part += (vv ? w_vv : w_rv) * (double)kv;
+      }
+    }
+    mmd = eval_block_sum(part, red);
+  }
+  if (threadIdx.x == 0) {
+    acc[0] += (double)B * mse;
+    acc[1] += (double)B * (mse + mmd);
+    acc[2] += (double)B;
+  }
+}
+
 // ---- Adam with its per-step state on the device (fastegnn_adam_step_dev).
 // The hazard: every workgroup of tensor t must see the SAME step count, so no workgroup of the element kernel may advance
 // steps_dev[t] while others still read it (and all of them must take the same skip decision, from a word that a host may clear at
@@ -380,6 +459,21 @@ int fastegnn_loss_mse_mmd_ragged(const float *loc_pred, const float *loc_t, cons
   FE_REQUIRE(sample_count || B == 0, "loss_mse_mmd_ragged: null sample_count (fastegnn_loss_mse_mmd is the form with full rows)");
   return loss_mse_mmd_launch(loc_pred, loc_t, vloc, sample_nodes, sample_count, N, B, C, S, sigma, weight, loss2, g_loc,
                              g_vloc, stream);
+}
+
+int fastegnn_loss_mse_mmd_eval(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                               const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
+                               float weight, double *acc, void *stream) {
+  FE_REQUIRE(acc, "loss_mse_mmd_eval: null acc (three doubles in device memory)");
+  FE_REQUIRE(N >= 0 && B >= 0 && C >= 0 && S >= 0, "loss_mse_mmd_eval: negative size");
+  FE_REQUIRE(C <= 256 && S <= 4096, "loss_mse_mmd_eval: C <= 256 and S <= 4096");
+  if (B == 0) return FASTEGNN_OK;   // no graph: acc stays as it is
+  const bool mmd = sample_nodes && S > 0;
+  FE_REQUIRE((N == 0 || (loc_pred && loc_t)) && (!mmd || (vloc && loc_pred)), "loss_mse_mmd_eval: null pointer");
+  const size_t lds = mmd ? (size_t)(3 * C + 3 * S) * sizeof(float) : 0;
+  hipLaunchKernelGGL(loss_eval_kernel, dim3(1), dim3(EVAL_THREADS), lds, (hipStream_t)stream, loc_pred, loc_t, vloc,
+                     mmd ? sample_nodes : nullptr, sample_count, (long)N * 3, B, C, S, sigma, weight, acc);
+  return check_launch("loss_eval_kernel");
 }
 
 int fastegnn_mmd_sample(const int64_t *ptr, int32_t B, int32_t S, uint64_t *rng, int32_t advance, int32_t *sample_nodes,

@@ -14,7 +14,8 @@ import torch
 from torch import nn
 
 from . import _lib as K
-from .model import RangeGuard, SortedGraph, _PadParams, _PtrTable, _activation_kind, _carve, _fill, _new_layer, _stream
+from .model import (STAGE_SET, RangeGuard, SortedGraph, _PadParams, _PtrTable, _activation_kind, _carve, _fill, _new_layer, _no_backward,
+                    _stream, inference_plan)
 
 H = K.H
 
@@ -73,6 +74,42 @@ def _egnn_pad_layout(name: str, shape, h: int):
         blocks, lead = [h], 0
     rows_dst = rows if head else H
     return rows, cols, rows_dst, blocks, (rows_dst, cols + sum(b // h * (H - h) for b in blocks)), lead
+
+
+def _egnn_forward_only(spec, graph, edge_fea, x, h_in, v, params):
+    """_EGNNFunction.forward without a backward to come (fastegnn_amd.model._forward_only): one stage set and the h / x ping-pong of
+    inference_plan(wiring="egnn") carved from one allocation per call, one weight-image buffer for all layers; the x_out / h_out of the
+    last layer are fresh tensors."""
+    lib = K.lib(act=spec.act_kind != K.ACT_SILU, wide=spec.wide)
+    ea_sorted = graph.permute(edge_fea.detach() if edge_fea is not None else None)
+    dev = x.device
+    st = _stream(dev)
+    N = x.size(0)
+    f32 = dict(dtype=torch.float32, device=dev)
+    params = [p.detach() for p in params]
+    x, h_in, v = x.detach().contiguous().float(), h_in.detach().contiguous().float(), v.detach().contiguous().float()
+    batch = torch.zeros(N, dtype=torch.int32, device=dev)
+    shapes, _ = inference_plan(N, 1, 0, spec.n_layers, "egnn")
+    buf = _carve(dev, shapes)
+    h = buf["h@0"] if spec.n_layers else torch.empty(N, H, **f32)   # (no layer: the embedding is what the caller gets)
+    K.check(lib.fastegnn_embed_forward(K.ptr(h_in), N, spec.nf, K.ptr(params[0]), K.ptr(params[1]), K.ptr(h), st), "fastegnn_embed_forward")
+    wpack = torch.empty((lib.fastegnn_wpack_floats(0) + 3) // 4 * 4, **f32)
+    for i in range(spec.n_layers):
+        tab = _PtrTable([params[s] if s is not None else None for s in spec.layer_slots[i]])
+        o = (i + 1) & 1
+        b = dict(h=h, x=x, wpack=wpack, **{k: buf[k] for k in STAGE_SET if k in buf})
+        if i == spec.n_layers - 1:
+            b.update(h_out=torch.empty(N, H, **f32), x_out=torch.empty(N, 3, **f32))
+        else:
+            b.update(h_out=buf[f"h@{o}"], x_out=buf[f"x@{o}"])
+        L = _new_layer(spec, N, 1, graph)
+        _fill(L, batch=batch, vel=v, params=tab.addr(), **b)
+        L.QX_src = b["QX"].data_ptr()
+        if ea_sorted is not None:
+            L.ea_sorted = ea_sorted.data_ptr()
+        K.check(lib.fastegnn_layer_forward(C.byref(L), st), f"fastegnn_layer_forward[egnn {i}]")
+        h, x = b["h_out"], b["x_out"]
+    return x, h
 
 
 class _EGNNFunction(torch.autograd.Function):
@@ -251,6 +288,11 @@ class EGNN(nn.Module):
             edge_fea = None
         vv = v if v is not None else torch.zeros_like(x)
         plist = self._plist
+        # a forward that can have no backward runs on the planned, reused buffers (_egnn_forward_only); everything else is the autograd path
+        forward_only = _no_backward([*plist, x, h, edge_fea, v])
+
+        def run(*args):
+            return _egnn_forward_only(*args) if forward_only else _EGNNFunction.apply(*args[:-1], *args[-1])
         if self.hidden_nf < H:   # 64-wide images of the parameters (fastegnn_pad_params; the reverse mode slices the gradients back)
             plist = list(_PadParams.apply(tuple(self._spec.names), self.hidden_nf, 0, _egnn_pad_layout, *plist))
         guard, spec = self._range, self._spec
@@ -258,12 +300,12 @@ class EGNN(nn.Module):
             guard.poll("EGNN", self._plist)      # no synchronisation: an overflow of an EARLIER pass switches the build here (model.RangeGuard)
         spec.wide = guard.wide
         spec.guard = None if guard.wide else guard
-        x_out, h_out = _EGNNFunction.apply(spec, graph, edge_fea, x, h, vv, *plist)
+        x_out, h_out = run(spec, graph, edge_fea, x, h, vv, plist)
         if not guard.wide:
             guard.launch(K.lib(act=spec.act_kind != K.ACT_SILU, wide=False), (x_out, h_out), (x, h))
             if guard.mode == "sync" and guard.sync_and_poll(x.device, "EGNN", self._plist):
                 spec.wide, spec.guard = True, None
-                x_out, h_out = _EGNNFunction.apply(spec, graph, edge_fea, x, h, vv, *plist)
+                x_out, h_out = run(spec, graph, edge_fea, x, h, vv, plist)
         if self.hidden_nf < H:
             h_out = h_out[:, :self.hidden_nf]     # the padded features are identically zero
         return (x_out, v, h_out) if v is not None else (x_out, h_out)

@@ -521,6 +521,119 @@ def _skip_last_node_update(spec) -> bool:
     return not (spec.flags & K.F_RF) and os.environ.get("FASTEGNN_KEEP_DEAD_NODE_UPDATE", "0") in ("", "0")
 
 
+# ------------------------------------------------------------------------------------------
+# forward-only execution: a forward that can have no backward runs on ONE set of stage buffers
+# ------------------------------------------------------------------------------------------
+STAGE_SET = ("P", "QX", "A", "svel", "sgrav", "xsum", "Bc", "aggm", "aggx", "npre", "poolV", "poolX")   # written and read inside one layer
+PING_PONG = ("h", "x", "Z", "HvT")                                                                      # a layer's inputs / the next one's
+
+
+def _padded(shape) -> int:
+    """floats a carved slice takes: its element count rounded up to 4 (16 bytes)"""
+    return (math.prod(shape) + 3) // 4 * 4
+
+
+def inference_plan(N: int, B: int, C_: int, n_layers: int, wiring: str = "fastegnn", dead_last: bool = True):
+    """Buffer plan of a forward-only pass of a fused model; pure host arithmetic (tests/test_inference_plan_cpu.py).
+    -> ({name: shape}, total floats).  One stage set (STAGE_SET) that every layer overwrites, then ``h / x / Z / HvT`` as ``"h@0"``,
+    ``"h@1"``, ...: layer i reads set i & 1 and writes set (i + 1) & 1 (layer 0 reads the caller's ``x`` and ``Z``).  What the LAST layer
+    returns to the caller is not planned: those are fresh allocations that never alias a reusable slice.  A slice takes ``_padded(shape)``
+    floats, in dict order, so every offset is a multiple of 16 bytes (``plan_offsets``); the total is the same for every
+    ``n_layers >= 2``.  ``wiring``: "fastegnn", "fastrf" (FASTEGNN_F_RF: its kernels take npre and poolV like FastEGNN's, and its last
+    layer still writes h_out / HvT_out, into the other set) or "egnn" (FASTEGNN_F_EGNN: no virtual nodes -- no sgrav / xsum / Bc / poolV
+    / poolX, no Z / HvT).  ``dead_last``: the last layer's node update is skipped (_skip_last_node_update), so a single-layer FastEGNN
+    plans neither npre nor poolV nor a second set."""
+    if wiring not in ("fastegnn", "fastrf", "egnn"):
+        raise ValueError(f"fastegnn_amd.inference_plan: unknown wiring {wiring!r}")
+    if min(N, B, C_, n_layers) < 0:
+        raise ValueError("fastegnn_amd.inference_plan: negative size")
+    egnn = wiring == "egnn"
+    stage = dict(P=(N, H), QX=(N, K.QX_LD), A=(N, H), svel=(N,), sgrav=(N,), xsum=(B, 4), Bc=(B, C_, H), aggm=(N, H), aggx=(N, 3),
+                 npre=(N, H), poolV=(B, C_, H), poolX=(B, 3, C_))
+    assert tuple(stage) == STAGE_SET
+    if egnn:
+        for k in ("sgrav", "xsum", "Bc", "poolV", "poolX"):
+            del stage[k]
+    last_writes_h = wiring == "fastrf" or (wiring == "fastegnn" and not dead_last)   # (EGNN's last h_out is returned: a fresh allocation)
+    if wiring == "fastegnn" and dead_last and n_layers <= 1:
+        del stage["npre"], stage["poolV"]
+    n_sets = 2 if n_layers >= 2 or (n_layers == 1 and last_writes_h) else 1
+    one = dict(h=(N, H), x=(N, 3)) if egnn else dict(h=(N, H), x=(N, 3), Z=(B, 3, C_), HvT=(B, C_, H))
+    shapes = dict(stage)
+    for s in range(n_sets):
+        shapes.update({f"{k}@{s}": v for k, v in one.items()})
+    return shapes, sum(_padded(s) for s in shapes.values())
+
+
+def plan_offsets(shapes: Dict[str, tuple]) -> Dict[str, int]:
+    """float offset of every slice of a plan inside its one allocation (the layout ``_carve`` gives)"""
+    out, off = {}, 0
+    for k, s in shapes.items():
+        out[k] = off
+        off += _padded(s)
+    return out
+
+
+def _no_backward(tensors) -> bool:
+    """can this forward have no backward?  grad mode off, or nothing floating-point among parameters and inputs requires grad"""
+    return not torch.is_grad_enabled() or not any(
+        isinstance(t, torch.Tensor) and t.is_floating_point() and t.requires_grad for t in tensors)
+
+
+def _forward_only(spec: "_Spec", graph: "SortedGraph", batch32, gptr, edge_attr, node_attr, node_feat, node_loc, node_vel, loc_mean,
+                  params):
+    """_FastEGNNFunction.forward without a backward to come: the same C-ABI calls on the planned buffers (inference_plan), carved from
+    ONE allocation of torch's caching allocator per call -- nothing is kept between calls, so the call is capturable and two streams
+    never share a buffer.  x_out / Z_out of the last layer are fresh tensors.  One weight-image buffer serves all layers: every
+    fastegnn_layer_forward packs its own images in front of its stages (stream order keeps the layer before from reading them late)."""
+    lib = K.lib(act=spec.act_kind != K.ACT_SILU, wide=spec.wide)
+    ea_sorted = graph.permute(edge_attr.detach() if edge_attr is not None else None)
+    node_attr = node_attr.detach().contiguous().float() if node_attr is not None else None
+    dev = node_loc.device
+    st = _stream(dev)
+    N, B, Cn = node_loc.size(0), loc_mean.size(0), spec.C
+    f32 = dict(dtype=torch.float32, device=dev)
+    params = [p.detach() for p in params]
+    for p in params:
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16:
+            raise RuntimeError("fastegnn_amd: parameters must be contiguous, 16-byte aligned fp32 tensors")
+    node_feat, node_loc, node_vel, loc_mean = (t.detach().contiguous().float() for t in (node_feat, node_loc, node_vel, loc_mean))
+    skip_last = _skip_last_node_update(spec)
+    rf = bool(spec.flags & K.F_RF)
+    shapes, _ = inference_plan(N, B, Cn, spec.n_layers, "fastrf" if rf else "fastegnn", dead_last=skip_last)
+    buf = _carve(dev, shapes)
+    h, HvT = buf["h@0"], buf["HvT@0"]
+    K.check(lib.fastegnn_embed_forward(K.ptr(node_feat), N, spec.nf, K.ptr(params[1]), K.ptr(params[2]), K.ptr(h), st),
+            "fastegnn_embed_forward")
+    K.check(lib.fastegnn_virtual_init(K.ptr(params[0]), B, Cn, K.ptr(HvT), st), "fastegnn_virtual_init")
+    x, Z = node_loc, loc_mean
+    wpack = torch.empty((lib.fastegnn_wpack_floats(Cn) + 3) // 4 * 4, **f32)
+    for i in range(spec.n_layers):
+        tab = _PtrTable([params[s] if s is not None else None for s in spec.layer_slots[i]])
+        last = i == spec.n_layers - 1
+        dead = skip_last and last                  # this layer's node update is read by nothing: its buffers stay null, as in the autograd path
+        o = (i + 1) & 1
+        b = dict(h=h, x=x, Z=Z, HvT=HvT, wpack=wpack, **{k: buf[k] for k in STAGE_SET if k in buf})
+        if dead:
+            b.pop("npre", None), b.pop("poolV", None)
+        if last:                                   # what the caller keeps never aliases the reusable slices
+            b.update(x_out=torch.empty(N, 3, **f32), Z_out=torch.empty(B, 3, Cn, **f32))
+        else:
+            b.update(x_out=buf[f"x@{o}"], Z_out=buf[f"Z@{o}"])
+        if not dead:
+            b.update(h_out=buf[f"h@{o}"], HvT_out=buf[f"HvT@{o}"])
+        L = _new_layer(spec, N, B, graph)
+        _fill(L, batch=batch32, gptr=gptr, vel=node_vel, params=tab.addr(), **b)
+        L.QX_src = b["QX"].data_ptr()
+        if ea_sorted is not None:
+            L.ea_sorted = ea_sorted.data_ptr()
+        if node_attr is not None:
+            L.node_attr = node_attr.data_ptr()
+        K.check(lib.fastegnn_layer_forward(C.byref(L), st), f"fastegnn_layer_forward[{i}]")
+        h, x, Z, HvT = b.get("h_out"), b["x_out"], b["Z_out"], b.get("HvT_out")
+    return x, Z
+
+
 class _FastEGNNFunction(torch.autograd.Function):
     """Whole-model forward/backward on the HIP library (one C-ABI call per layer and direction)."""
 
@@ -842,6 +955,8 @@ class FastEGNN(nn.Module):
         if edge_attr is not None and edge_attr.size(1) == 0:
             edge_attr = None
         plist = self._plist
+        # a forward that can have no backward runs on the planned, reused buffers (_forward_only); everything else is the autograd path as it was
+        forward_only = _no_backward([*plist, node_feat, node_loc, node_vel, loc_mean, edge_attr, node_attr])
         if self.hidden_nf < H:
             rf = bool(spec.flags & K.F_RF)
             plist = list(_PadParams.apply(tuple(spec.names), self.hidden_nf, spec.C, rf, *plist))
@@ -853,6 +968,8 @@ class FastEGNN(nn.Module):
         spec.guard = guard if guarded and not guard.wide else None
 
         def run():
+            if forward_only:
+                return _forward_only(spec, graph, batch32, gptr, edge_attr, node_attr, node_feat, node_loc, node_vel, loc_mean, plist)
             return _FastEGNNFunction.apply(spec, graph, batch32, gptr, edge_attr, node_attr, node_feat, node_loc, node_vel,
                                            loc_mean, *plist)
         out = run()

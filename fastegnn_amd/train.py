@@ -68,6 +68,37 @@ def mse_mmd_loss(loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_coun
     return loss, loss2[1]
 
 
+def mse_mmd_eval(loc_pred, vloc, loc_t, acc, sigma, weight, sample_nodes=None, sample_count=None):
+    """The loss of a forward-only batch, summed on the device (fastegnn_loss_mse_mmd_eval; utils/train.py:104-108,163-165 with
+    backprop=False).  ``acc``: float64 [3] on the GPU, read and advanced: ``acc[0] += B * MSE`` (what the reference logs, train.py:107),
+    ``acc[1] += B * (MSE + weight * (l_vv - l_rv))``, ``acc[2] += B``, with ``B = vloc.size(0)`` (or ``B = vloc`` where ``vloc`` is an int:
+    a model without virtual nodes, no MMD term).  ``sample_nodes`` / ``sample_count`` as ``mse_mmd_loss``; ``sample_nodes=None``: the MMD
+    term is not evaluated and ``acc[1]`` advances by ``B * MSE``.  No gradients, no read-back, no synchronisation; capturable; two runs
+    from the same ``acc`` give the same bits.  -> ``acc``."""
+    if not (isinstance(acc, torch.Tensor) and acc.is_cuda and acc.dtype == torch.float64 and acc.numel() == 3 and acc.is_contiguous()):
+        raise ValueError("fastegnn_amd.mse_mmd_eval: acc must be a contiguous float64 tensor of 3 elements on the GPU")
+    dev = loc_pred.device
+    loc_pred, loc_t = loc_pred.detach().contiguous().float(), loc_t.detach().contiguous().float()
+    N = loc_pred.size(0)
+    if isinstance(vloc, torch.Tensor):
+        vloc = vloc.detach().contiguous().float()
+        B, Cn = vloc.size(0), vloc.size(2)
+    else:
+        B, Cn, vloc, sample_nodes = int(vloc), 0, None, None
+    samp = cnt = None
+    S = 0
+    if sample_nodes is not None:
+        S = sample_nodes.size(1)
+        samp = sample_nodes.to(torch.int32).contiguous()
+        if sample_count is not None:
+            if sample_count.numel() != B:
+                raise ValueError(f"fastegnn_amd.mse_mmd_eval: sample_count has {sample_count.numel()} entries for {B} graphs")
+            cnt = sample_count.to(torch.int32).contiguous()
+    K.check(K.lib().fastegnn_loss_mse_mmd_eval(K.ptr(loc_pred), K.ptr(loc_t), K.ptr(vloc), K.ptr(samp), K.ptr(cnt), N, B, Cn, S,
+                                               float(sigma), float(weight), K.ptr(acc), _stream(dev)), "fastegnn_loss_mse_mmd_eval")
+    return acc
+
+
 def _u64(v):
     return int(v) & 0xFFFFFFFFFFFFFFFF
 
@@ -368,3 +399,58 @@ def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, wei
         return loss, mse
     optimizer.step()
     return loss, mse
+
+
+def _evaluate_pass(model, loader, sigma, weight, sampler, num_sample):
+    """one forward-only sweep over the loader -> the device accumulator (None for an empty loader); nothing is read back"""
+    acc = None
+    egnn = type(model).__name__ == "EGNN"
+    for data in loader:
+        loc_0 = data["loc_0"]
+        if acc is None:
+            acc = torch.zeros(3, dtype=torch.float64, device=loc_0.device)
+        edge_attr = augment_edge_attr(data.get("edge_attr"), loc_0, data["edge_index"])
+        if egnn:   # utils/train.py:66-68: no virtual nodes, no MMD term
+            out = model(x=loc_0, h=data["node_feat"], edge_index=data["edge_index"], edge_fea=edge_attr, v=data["vel_0"])
+            n_graphs = data["ptr"].numel() - 1 if "ptr" in data else data["loc_mean"].size(0)
+            mse_mmd_eval(out[0], n_graphs, data["loc_t"], acc, sigma, weight)
+            continue
+        loc_pred, vloc = model(node_loc=loc_0, node_vel=data["vel_0"], node_attr=None, node_feat=data["node_feat"],
+                               edge_index=data["edge_index"], loc_mean=data["loc_mean"], data_batch=data["batch"], edge_attr=edge_attr)
+        nodes = count = None
+        if sampler is not None:
+            nodes, count = sampler.draw(data["ptr"], min(int(num_sample), loc_0.size(0)))
+        mse_mmd_eval(loc_pred, vloc, data["loc_t"], acc, sigma, weight, nodes, count)
+    return acc
+
+
+def evaluate(model, loader, sigma, weight, *, sampler: Optional[MMDSampler] = None, num_sample: Optional[int] = None) -> dict:
+    """The reference's ``train_single_epoch(..., backprop=False)`` (utils/train.py:23-179: its validation and test epochs) ->
+    ``dict(mse=, loss=, graphs=)``.  ``loader`` yields the collated batches ``train_step`` takes.  The model is put into ``eval()`` (its
+    previous mode is restored) and runs under ``torch.no_grad()`` -- the fused models then take their forward-only path, on one reused
+    set of stage buffers -- and every batch adds its loss into three fp64 words on the device (``mse_mmd_eval``): ONE read-back, after
+    the last batch.  ``mse`` is the graph-weighted mean MSE, the number the reference prints and early-stops on; ``loss`` adds the MMD
+    term when a ``sampler`` (with ``num_sample``, the reference's ``sample * C``) draws the nodes for it -- without one the term is
+    skipped and ``loss == mse`` (the reference computes it in these epochs and throws it away).
+    After the read-back the model's range guard is polled once: if a batch left the operand range of the f16x2 build the module has
+    moved to the wide-range build (one warning, fastegnn_amd.model.RangeGuard), and the loader is run ONCE more on that build and that
+    result returned (a sampler draws fresh samples for it); still non-finite numbers are returned as they are."""
+    if sampler is not None and num_sample is None:
+        raise ValueError("fastegnn_amd.evaluate: a sampler needs num_sample (the reference's sample * C)")
+    guard = getattr(model, "_range", None)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            wide_before = guard.wide if guard is not None else True
+            acc = _evaluate_pass(model, loader, sigma, weight, sampler, num_sample)
+            if acc is None:
+                return dict(mse=float("nan"), loss=float("nan"), graphs=0)
+            host = acc.tolist()   # the one synchronisation of the epoch
+            if guard is not None and not wide_before:
+                guard.poll(type(model).__name__, getattr(model, "_plist", None), why="a forward-only epoch (evaluate)")
+                if guard.wide:    # switched by this poll or by a forward of the sweep: some batch returned non-finite outputs
+                    host = _evaluate_pass(model, loader, sigma, weight, sampler, num_sample).tolist()
+    finally:
+        model.train(was_training)
+    return dict(mse=host[0] / host[2], loss=host[1] / host[2], graphs=int(host[2]))

@@ -489,6 +489,24 @@ int fastegnn_mmd_sample(const int64_t *ptr, int32_t B, int32_t S, uint64_t *rng,
 int fastegnn_loss_mse_mmd_ragged(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
                                  const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
                                  float weight, float *loss2, float *g_loc, float *g_vloc, void *stream);
+/* The loss of a forward-only epoch (utils/train.py:104-108,163-165 with backprop=False): the same two numbers, NO gradient
+ * outputs, summed over the batches of a loader on the device.  ADDITIVE export, found by symbol: FASTEGNN_ABI_VERSION stays 108.
+ *   acc  DEVICE double[3], read and advanced by this call:
+ *     acc[0] += B * MSE(loc_pred, loc_t)            (the number the reference logs: train.py:107)
+ *     acc[1] += B * (MSE + weight * (l_vv - l_rv))  (the full objective)
+ *     acc[2] += B
+ * so that acc[0] / acc[2] after the last batch is the reference's result['loss'] / result['counter'].
+ * sample_nodes / sample_count as fastegnn_loss_mse_mmd_ragged (sample_count null: every row full); sample_nodes null or S == 0: the
+ * MMD term is not evaluated at all (l_vv neither) and acc[1] advances by B * MSE.
+ * Every sum is taken in fp64 (the differences and squares of the MSE exactly; the kernel values exp(-d / 2 sigma^2) are the fp32
+ * ones of the training loss) by ONE workgroup in a fixed order: the argument list carries no workspace for workgroup partials, so
+ * the fixed-order final workgroup of fastegnn_grad_sqnorm's scheme is the only one.  No atomics: two calls on the same inputs from
+ * the same acc leave bit-identical acc.  Reads nothing back, synchronises nothing, capturable.  B == 0 launches nothing and leaves acc
+ * as it is.  FASTEGNN_E_INVALID before any launch for: null acc, a null tensor that would be read, N < 0, B < 0, C < 0, S < 0,
+ * C > 256 or S > 4096 (the ceilings of the training loss). */
+int fastegnn_loss_mse_mmd_eval(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                               const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
+                               float weight, double *acc, void *stream);
 
 /* ---- graph construction on device (datasets/simulation/dataset.py:80,96-101) ----
  * radius graph without self loops: all ordered pairs (i, j != i) with |x_i - x_j|^2 <= r^2 (fp32, each
