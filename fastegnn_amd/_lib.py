@@ -186,6 +186,14 @@ def lib(act: bool = False, wide=None):
     L.fastegnn_cutoff_tmp_bytes.argtypes = [C.c_int64]
     L.fastegnn_cutoff_edges.argtypes = [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]
     L.fastegnn_nbody_cutoff_edges.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp]
+    # B ragged clouds per call: additive
+    L.fastegnn_radius_graph_batch_ws_bytes.restype = C.c_size_t
+    L.fastegnn_radius_graph_batch_ws_bytes.argtypes = [_i32, _i32]
+    L.fastegnn_radius_graph_batch_count.argtypes = [_vp, _vp, _i32, _i32, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]
+    L.fastegnn_radius_graph_batch_fill.argtypes = [_vp, _vp, _i32, _i32, C.c_float, _vp, C.c_size_t, C.c_int64, _vp, _vp, _vp, _vp]
+    L.fastegnn_cutoff_batch_tmp_bytes.restype = C.c_size_t
+    L.fastegnn_cutoff_batch_tmp_bytes.argtypes = [C.c_int64, _i32]
+    L.fastegnn_cutoff_edges_batch.argtypes = [_vp, _vp, _vp, _vp, _i32, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]
     L.fastegnn_selftest_gemm.argtypes = [_vp, _vp, _vp, _i32, _vp]
     L.fastegnn_selftest_rm.argtypes = [_vp, _vp, _vp, _i32, _i32, _vp]
     L.fastegnn_selftest_jreduce.argtypes = [_vp, _vp, _vp]
@@ -278,6 +286,8 @@ EXPORTED = STAGE_FUNCS + [
     "fastegnn_mmd_sample", "fastegnn_loss_mse_mmd_ragged", "fastegnn_loss_mse_mmd_eval",
     "fastegnn_radius_graph_ws_bytes", "fastegnn_radius_graph_count", "fastegnn_radius_graph_fill",
     "fastegnn_cutoff_tmp_bytes", "fastegnn_cutoff_edges", "fastegnn_nbody_cutoff_edges",
+    "fastegnn_radius_graph_batch_ws_bytes", "fastegnn_radius_graph_batch_count", "fastegnn_radius_graph_batch_fill",
+    "fastegnn_cutoff_batch_tmp_bytes", "fastegnn_cutoff_edges_batch",
     "fastegnn_profile_enable", "fastegnn_profile_kernels", "fastegnn_profile_name", "fastegnn_profile_collect",
     "fastegnn_comm_unique_id_bytes", "fastegnn_comm_unique_id", "fastegnn_comm_init", "fastegnn_comm_destroy", "fastegnn_comm_rank",
     "fastegnn_comm_world", "fastegnn_comm_all_reduce", "fastegnn_comm_all_gather", "fastegnn_comm_reduce_scatter",

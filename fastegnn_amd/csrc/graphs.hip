@@ -5,6 +5,7 @@
 // Two passes (count, fill) so that the caller allocates the exact edge list; edges come out grouped by
 // centre node with neighbours in ascending index order (deterministic).
 #include <cstring>
+#include <vector>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include "kernels.h"
@@ -46,20 +47,23 @@ __global__ __launch_bounds__(256) void bbox_kernel(const float *loc, int N, unsi
 
 // grid from the bounding box: cell edge = max(r, extent / 255), and the per-axis cell count is clamped to 256, so
 // that there are at most 256^3 = 2^24 cells (floor(extent / cell) + 1 <= 256; the clamp covers rounding)
-__global__ void grid_kernel(const unsigned *box, float r, Grid *g) {
-  if (threadIdx.x != 0) return;
+__device__ __forceinline__ void grid_from_box(const float lo[3], const float hi[3], float r, Grid *g) {
   float cell = r;
   for (int k = 0; k < 3; ++k) {
-    const float lo = key2f(box[k]), hi = key2f(box[3 + k]);
-    g->lo[k] = lo;
-    cell = fmaxf(cell, (hi - lo) / 255.0f);
+    g->lo[k] = lo[k];
+    cell = fmaxf(cell, (hi[k] - lo[k]) / 255.0f);
   }
   g->inv = 1.0f / cell;
   for (int k = 0; k < 3; ++k) {
-    const float lo = key2f(box[k]), hi = key2f(box[3 + k]);
-    const int n = (int)((hi - lo) * g->inv) + 1;
+    const int n = (int)((hi[k] - lo[k]) * g->inv) + 1;
     g->n[k] = n > 256 ? 256 : n;   // cell_of clamps the coordinates of the last cell accordingly
   }
+}
+__global__ void grid_kernel(const unsigned *box, float r, Grid *g) {
+  if (threadIdx.x != 0) return;
+  float lo[3], hi[3];
+  for (int k = 0; k < 3; ++k) { lo[k] = key2f(box[k]); hi[k] = key2f(box[3 + k]); }
+  grid_from_box(lo, hi, r, g);
 }
 __device__ __forceinline__ void cell_of(const Grid &g, const float *p, int c[3]) {
   for (int k = 0; k < 3; ++k) {
@@ -169,7 +173,214 @@ __global__ void take_edges_kernel(const int64_t *ei, const float *dist, const in
   if (dist_out) dist_out[k] = dist[s];
 }
 
+// ---------------------------------------------------------------- B ragged clouds in one call
+// loc [N,3] holds the clouds back to back, ptr int64 [B+1] their node ranges.  Every graph has its own Grid (the single-cloud
+// rule on its own bounding box); ONE radix sort on the key (graph << 24 | cell id) orders the points of a graph by cell inside
+// the graph's own node range, and a run of cells is found by binary search in that range: no table over the 2^24 cells.
+
+// node range of graph b, clamped to 0 <= s <= e <= N: a malformed ptr sets the status word, it never indexes outside loc
+__device__ __forceinline__ void graph_range(const int64_t *ptr, int b, int N, int &s, int &e) {
+  int64_t a = ptr[b], z = ptr[b + 1];
+  a = a < 0 ? 0 : (a > N ? N : a);
+  z = z < a ? a : (z > N ? N : z);
+  s = (int)a;
+  e = (int)z;
+}
+// the segment that holds position v: the largest b in [0, B-1] with p[b] <= v (p ascending prefix sums, p[0] = 0 <= v)
+__device__ __forceinline__ int segment_of(const int64_t *p, int B, int64_t v) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (p[mid] <= v) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// one workgroup per graph: checks its piece of ptr, reduces the bounding box of its points, writes its Grid
+__global__ __launch_bounds__(256) void batch_grid_kernel(const float *loc, const int64_t *ptr, int N, int B, float r, Grid *grids,
+                                                         int *status) {
+  __shared__ float red[4][6];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) {
+    const int64_t a = ptr[b], z = ptr[b + 1];
+    if (a > z || (b == 0 && a != 0) || (b == B - 1 && z != N)) atomicOr(status, 1);
+  }
+  int s, e;
+  graph_range(ptr, b, N, s, e);
+  float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+  for (int i = s + tid; i < e; i += 256)
+    for (int k = 0; k < 3; ++k) {
+      const float v = loc[(size_t)i * 3 + k];
+      mn[k] = fminf(mn[k], v);
+      mx[k] = fmaxf(mx[k], v);
+    }
+  for (int k = 0; k < 3; ++k) {
+    for (int off = 32; off > 0; off >>= 1) {
+      mn[k] = fminf(mn[k], __shfl_xor(mn[k], off));
+      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], off));
+    }
+    if ((tid & 63) == 0) {
+      red[tid >> 6][k] = mn[k];
+      red[tid >> 6][3 + k] = mx[k];
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  float lo[3], hi[3];
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = fminf(fminf(red[0][k], red[1][k]), fminf(red[2][k], red[3][k]));
+    hi[k] = fmaxf(fmaxf(red[0][3 + k], red[1][3 + k]), fmaxf(red[2][3 + k], red[3][3 + k]));
+    if (s == e) lo[k] = hi[k] = 0.f;   // an empty graph: a valid one-cell grid that nothing looks up
+  }
+  grid_from_box(lo, hi, r, grids + b);
+}
+
+__global__ void batch_key_kernel(const float *loc, const int64_t *ptr, int N, int B, const Grid *grids, int32_t *gid,
+                                 unsigned long long *key, int32_t *idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int b = segment_of(ptr, B, i);
+  int c[3];
+  const Grid g = grids[b];
+  cell_of(g, loc + (size_t)i * 3, c);
+  gid[i] = b;
+  key[i] = ((unsigned long long)b << 24) | (unsigned)((c[2] * g.n[1] + c[1]) * g.n[0] + c[0]);
+  idx[i] = i;
+}
+
+// radius_kernel for the batch: the candidates of centre i are the x-runs of cells of ITS graph, each found by a lower-bound
+// search in the graph's range [s, e) of the sorted keys and walked until the key leaves the run.  E bounds every write.
+template <bool FILL>
+__global__ __launch_bounds__(256) void batch_radius_kernel(const float *loc, const int64_t *ptr, int N, const Grid *grids,
+                                                           const int32_t *gid, const unsigned long long *sorted_key,
+                                                           const int32_t *sorted_idx, float r2, int64_t *deg, const int64_t *offs,
+                                                           int64_t *edge_index, float *dist, int64_t E) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int b = gid[i];
+  int s, e;
+  graph_range(ptr, b, N, s, e);
+  const Grid g = grids[b];
+  const unsigned long long kb = (unsigned long long)b << 24;
+  const float pi[3] = {loc[(size_t)i * 3], loc[(size_t)i * 3 + 1], loc[(size_t)i * 3 + 2]};
+  int c[3];
+  cell_of(g, pi, c);
+  int64_t cnt = 0;
+  const int64_t base = FILL ? offs[i] : 0;
+  const int64_t room = FILL ? (base < E ? E - base : 0) : 0;
+  for (int dz = -1; dz <= 1; ++dz) {
+    const int z = c[2] + dz;
+    if (z < 0 || z >= g.n[2]) continue;
+    for (int dy = -1; dy <= 1; ++dy) {
+      const int y = c[1] + dy;
+      if (y < 0 || y >= g.n[1]) continue;
+      const int x0 = max(c[0] - 1, 0), x1 = min(c[0] + 1, g.n[0] - 1);
+      const unsigned long long key0 = kb + (unsigned)((z * g.n[1] + y) * g.n[0] + x0), key1 = key0 + (unsigned)(x1 - x0 + 1);
+      int lo = s, hi = e;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted_key[mid] < key0) lo = mid + 1; else hi = mid;
+      }
+      for (int k = lo; k < e && sorted_key[k] < key1; ++k) {
+        const int j = sorted_idx[k];
+        if (j == i) continue;
+        const float pj[3] = {loc[(size_t)j * 3], loc[(size_t)j * 3 + 1], loc[(size_t)j * 3 + 2]};
+        const float d2 = dist2(pi, pj);
+        if (d2 <= r2) {
+          if (FILL && cnt < room) {
+            edge_index[base + cnt] = i;
+            edge_index[E + base + cnt] = j;
+            dist[base + cnt] = sqrtf(d2);
+          }
+          ++cnt;
+        }
+      }
+    }
+  }
+  if (!FILL) deg[i] = cnt;
+  if (FILL) {   // ascending neighbour order, as radius_kernel does it
+    if (cnt > room) cnt = room;
+    for (int64_t a = 1; a < cnt; ++a) {
+      const int64_t cj = edge_index[E + base + a];
+      const float cd = dist[base + a];
+      int64_t q = a - 1;
+      while (q >= 0 && edge_index[E + base + q] > cj) {
+        edge_index[E + base + q + 1] = edge_index[E + base + q];
+        dist[base + q + 1] = dist[base + q];
+        --q;
+      }
+      edge_index[E + base + q + 1] = cj;
+      dist[base + q + 1] = cd;
+    }
+  }
+}
+
+// eptr[b] = offs[ptr[b]] for b in [0, B], eptr[B + 1] = the status word: what the count call reads back in one copy
+__global__ void batch_edge_ptr_kernel(const int64_t *ptr, int N, int B, const int64_t *offs, const int *status, int64_t *eptr) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b > B + 1) return;
+  if (b == B + 1) { eptr[b] = *status; return; }
+  int64_t a = ptr[b];
+  a = a < 0 ? 0 : (a > N ? N : a);
+  eptr[b] = offs[a];
+}
+
+// segmented cutoff: key (graph << 32 | distance bits), so that one stable sort orders every graph's edges by length in place
+__global__ void batch_cut_keys_kernel(const float *dist, const int64_t *edge_ptr, int B, int64_t E, unsigned long long *keys,
+                                      int32_t *vals) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= E) return;
+  keys[k] = ((unsigned long long)segment_of(edge_ptr, B, k) << 32) | __float_as_uint(dist[k]);
+  vals[k] = (int32_t)k;
+}
+// output position p belongs to the graph b whose keep range holds it and takes the (p - keep_ptr[b])-th shortest edge of b
+__global__ void batch_take_kernel(const int64_t *ei, const float *dist, const int32_t *order, const int64_t *edge_ptr,
+                                  const int64_t *keep_ptr, int B, int64_t E, int64_t keep, int64_t *ei_out, float *dist_out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= keep) return;
+  const int b = segment_of(keep_ptr, B, p);
+  int64_t q = edge_ptr[b] + (p - keep_ptr[b]);
+  q = q < 0 ? 0 : (q >= E ? E - 1 : q);   // prefix sums that do not fit each other still read inside the list
+  const int32_t s = order[q];
+  ei_out[p] = ei[s];
+  ei_out[keep + p] = ei[E + s];
+  if (dist_out) dist_out[p] = dist[s];
+}
+
 static size_t al(size_t x) { return (x + 255) / 256 * 256; }
+// bits needed for the values 0 .. n-1
+static int bits_for(int n) {
+  int b = 0;
+  while (b < 31 && (1ll << b) < n) ++b;
+  return b;
+}
+struct RgbWs {   // layout of the batched call's workspace: grows with N and B only
+  int *status; Grid *grids; int32_t *gid, *idx, *idx_s; unsigned long long *key, *key_s; int64_t *deg, *offs, *eptr; void *tmp;
+  size_t tmp_bytes;
+};
+static size_t rgb_sort_tmp_bytes(int N) { return 2 * al((size_t)N * 8) + 2 * al((size_t)N * 4) + (1u << 20); }
+static size_t rgb_fixed_bytes(int N, int B) {
+  return 256 + al((size_t)B * sizeof(Grid)) + 3 * al((size_t)N * 4) + 2 * al((size_t)N * 8) + 2 * al((size_t)(N + 1) * 8) +
+         al((size_t)(B + 2) * 8);
+}
+static RgbWs carve_batch_ws(void *ws, size_t bytes, int N, int B) {
+  char *p = (char *)ws;
+  RgbWs w;
+  w.status = (int *)p; p += 256;
+  w.grids = (Grid *)p; p += al((size_t)B * sizeof(Grid));
+  w.gid = (int32_t *)p; p += al((size_t)N * 4);
+  w.idx = (int32_t *)p; p += al((size_t)N * 4);
+  w.idx_s = (int32_t *)p; p += al((size_t)N * 4);
+  w.key = (unsigned long long *)p; p += al((size_t)N * 8);
+  w.key_s = (unsigned long long *)p; p += al((size_t)N * 8);
+  w.deg = (int64_t *)p; p += al((size_t)(N + 1) * 8);
+  w.offs = (int64_t *)p; p += al((size_t)(N + 1) * 8);
+  w.eptr = (int64_t *)p; p += al((size_t)(B + 2) * 8);
+  w.tmp = p;
+  w.tmp_bytes = bytes - (size_t)(p - (char *)ws);
+  return w;
+}
+
 struct RgWs {   // layout of the caller's workspace
   unsigned *box; Grid *grid; int32_t *cid, *idx, *cid_s, *idx_s, *start; int64_t *deg, *offs; void *tmp; size_t tmp_bytes;
 };
@@ -321,6 +532,119 @@ int fastegnn_cutoff_edges(const int64_t *edge_index, const float *dist, int64_t 
   hipLaunchKernelGGL(take_edges_kernel, dim3(cdiv(keep, 256)), dim3(256), 0, st, edge_index, dist, vals_s, E, keep,
                      edge_index_out, dist_out);
   return check_launch("cutoff_edges");
+}
+
+size_t fastegnn_radius_graph_batch_ws_bytes(int32_t N, int32_t B) {
+  if (N < 0) N = 0;
+  if (B < 0) B = 0;
+  return rgb_fixed_bytes(N, B) + rgb_sort_tmp_bytes(N);
+}
+
+int fastegnn_radius_graph_batch_count(const float *loc, const int64_t *ptr, int32_t N, int32_t B, float r, void *ws,
+                                      size_t ws_bytes, int64_t *edge_ptr_host, void *stream) {
+  FE_REQUIRE(N >= 0, "radius_graph_batch_count: N < 0");
+  FE_REQUIRE(B >= 0, "radius_graph_batch_count: B < 0");
+  FE_REQUIRE(r > 0.f, "radius_graph_batch_count: r must be positive");
+  FE_REQUIRE(edge_ptr_host, "radius_graph_batch_count: null edge_ptr_host");
+  if (N == 0 || B == 0) {
+    memset(edge_ptr_host, 0, ((size_t)B + 1) * 8);
+    return FASTEGNN_OK;
+  }
+  FE_REQUIRE(loc && ptr && ws, "radius_graph_batch_count: null pointer");
+  FE_REQUIRE(ws_bytes >= fastegnn_radius_graph_batch_ws_bytes(N, B), "radius_graph_batch_count: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope _ps(K_MISC, st);
+  RgbWs w = carve_batch_ws(ws, ws_bytes, N, B);
+  (void)hipMemsetAsync(w.status, 0, sizeof(int), st);
+  hipLaunchKernelGGL(batch_grid_kernel, dim3(B), dim3(256), 0, st, loc, ptr, N, B, r, w.grids, w.status);
+  hipLaunchKernelGGL(batch_key_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, loc, ptr, N, B, (const Grid *)w.grids, w.gid, w.key,
+                     w.idx);
+  const unsigned end_bit = 24 + bits_for(B);   // the key bits in use: 24 of the cell id, then the graph's
+  size_t need = 0;
+  hipError_t e = rocprim::radix_sort_pairs(nullptr, need, w.key, w.key_s, w.idx, w.idx_s, (size_t)N, 0, end_bit, st);
+  if (e != hipSuccess || need > w.tmp_bytes) { set_error("radius_graph_batch_count: sort workspace"); return FASTEGNN_E_INVALID; }
+  e = rocprim::radix_sort_pairs(w.tmp, need, w.key, w.key_s, w.idx, w.idx_s, (size_t)N, 0, end_bit, st);
+  if (e != hipSuccess) { set_error("radius_graph_batch_count: sort failed"); return FASTEGNN_E_LAUNCH; }
+  hipLaunchKernelGGL(batch_radius_kernel<false>, dim3(cdiv(N, 256)), dim3(256), 0, st, loc, ptr, N, (const Grid *)w.grids,
+                     (const int32_t *)w.gid, (const unsigned long long *)w.key_s, (const int32_t *)w.idx_s, r * r, w.deg,
+                     (const int64_t *)nullptr, (int64_t *)nullptr, (float *)nullptr, (int64_t)0);
+  (void)hipMemsetAsync(w.deg + N, 0, 8, st);   // exclusive scan of the degrees (+ total at position N)
+  need = 0;
+  e = rocprim::exclusive_scan(nullptr, need, w.deg, w.offs, (int64_t)0, (size_t)N + 1, rocprim::plus<int64_t>(), st);
+  if (e != hipSuccess || need > w.tmp_bytes) { set_error("radius_graph_batch_count: scan workspace"); return FASTEGNN_E_INVALID; }
+  e = rocprim::exclusive_scan(w.tmp, need, w.deg, w.offs, (int64_t)0, (size_t)N + 1, rocprim::plus<int64_t>(), st);
+  if (e != hipSuccess) { set_error("radius_graph_batch_count: scan failed"); return FASTEGNN_E_LAUNCH; }
+  hipLaunchKernelGGL(batch_edge_ptr_kernel, dim3(cdiv(B + 2, 256)), dim3(256), 0, st, ptr, N, B, (const int64_t *)w.offs,
+                     (const int *)w.status, w.eptr);
+  std::vector<int64_t> host((size_t)B + 2);   // edge_ptr [B+1] and the status word: the call's one read-back
+  if (hipMemcpyAsync(host.data(), w.eptr, ((size_t)B + 2) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return check_launch("radius_graph_batch_count(readback)");
+  const int rc = check_launch("radius_graph_batch_count");
+  if (rc != FASTEGNN_OK) return rc;
+  FE_REQUIRE(host[(size_t)B + 1] == 0, "radius_graph_batch_count: ptr is not 0 = ptr[0] <= ... <= ptr[B] = N");
+  memcpy(edge_ptr_host, host.data(), ((size_t)B + 1) * 8);
+  return FASTEGNN_OK;
+}
+
+int fastegnn_radius_graph_batch_fill(const float *loc, const int64_t *ptr, int32_t N, int32_t B, float r, void *ws,
+                                     size_t ws_bytes, int64_t n_edges, int64_t *edge_index, float *dist, int64_t *edge_ptr,
+                                     void *stream) {
+  FE_REQUIRE(N >= 0, "radius_graph_batch_fill: N < 0");
+  FE_REQUIRE(B >= 0, "radius_graph_batch_fill: B < 0");
+  FE_REQUIRE(r > 0.f, "radius_graph_batch_fill: r must be positive");
+  FE_REQUIRE(n_edges >= 0 && n_edges < (1ll << 31), "radius_graph_batch_fill: n_edges out of range (0 .. 2^31 - 1)");
+  hipStream_t st = (hipStream_t)stream;
+  if (N == 0 || B == 0) {
+    FE_REQUIRE(n_edges == 0, "radius_graph_batch_fill: edges without nodes or graphs");
+    if (edge_ptr) (void)hipMemsetAsync(edge_ptr, 0, ((size_t)B + 1) * 8, st);
+    return FASTEGNN_OK;
+  }
+  FE_REQUIRE(loc && ptr && ws && edge_ptr && (n_edges == 0 || (edge_index && dist)), "radius_graph_batch_fill: null pointer");
+  FE_REQUIRE(ws_bytes >= fastegnn_radius_graph_batch_ws_bytes(N, B), "radius_graph_batch_fill: workspace too small");
+  ProfScope _ps(K_MISC, st);
+  RgbWs w = carve_batch_ws(ws, ws_bytes, N, B);
+  (void)hipMemcpyAsync(edge_ptr, w.eptr, ((size_t)B + 1) * 8, hipMemcpyDeviceToDevice, st);
+  if (n_edges > 0)
+    hipLaunchKernelGGL(batch_radius_kernel<true>, dim3(cdiv(N, 256)), dim3(256), 0, st, loc, ptr, N, (const Grid *)w.grids,
+                       (const int32_t *)w.gid, (const unsigned long long *)w.key_s, (const int32_t *)w.idx_s, r * r,
+                       (int64_t *)nullptr, (const int64_t *)w.offs, edge_index, dist, n_edges);
+  return check_launch("radius_graph_batch_fill");
+}
+
+size_t fastegnn_cutoff_batch_tmp_bytes(int64_t E, int32_t B) {
+  if (E < 0) E = 0;
+  (void)B;   // the graphs only widen the sort key; every array is per edge
+  return 2 * al((size_t)E * 8) + 2 * al((size_t)E * 4) + al((size_t)E * 8) + 2 * al((size_t)E * 4) + (1u << 20);
+}
+
+int fastegnn_cutoff_edges_batch(const int64_t *edge_index, const float *dist, const int64_t *edge_ptr, const int64_t *keep_ptr,
+                                int32_t B, int64_t E, int64_t keep_total, int64_t *edge_index_out, float *dist_out, void *tmp,
+                                size_t tmp_bytes, void *stream) {
+  FE_REQUIRE(B >= 0, "cutoff_edges_batch: B < 0");
+  FE_REQUIRE(E >= 0 && E < (1ll << 31), "cutoff_edges_batch: E out of range (0 .. 2^31 - 1)");
+  FE_REQUIRE(keep_total >= 0 && keep_total <= E, "cutoff_edges_batch: keep_total out of range (0 .. E)");
+  if (keep_total == 0 || B == 0) return FASTEGNN_OK;
+  FE_REQUIRE(edge_index && dist && edge_ptr && keep_ptr && edge_index_out && tmp, "cutoff_edges_batch: null pointer");
+  FE_REQUIRE(tmp_bytes >= fastegnn_cutoff_batch_tmp_bytes(E, B), "cutoff_edges_batch: tmp too small");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope _ps(K_MISC, st);
+  char *p = (char *)tmp;
+  unsigned long long *keys = (unsigned long long *)p; p += al((size_t)E * 8);
+  unsigned long long *keys_s = (unsigned long long *)p; p += al((size_t)E * 8);
+  int32_t *vals = (int32_t *)p; p += al((size_t)E * 4);
+  int32_t *vals_s = (int32_t *)p; p += al((size_t)E * 4);
+  const size_t avail = tmp_bytes - (size_t)(p - (char *)tmp);
+  hipLaunchKernelGGL(batch_cut_keys_kernel, dim3(cdiv(E, 256)), dim3(256), 0, st, dist, edge_ptr, B, E, keys, vals);
+  const unsigned end_bit = 32 + bits_for(B);
+  size_t need = 0;
+  hipError_t e = rocprim::radix_sort_pairs(nullptr, need, keys, keys_s, vals, vals_s, (size_t)E, 0, end_bit, st);
+  if (e != hipSuccess || need > avail) { set_error("cutoff_edges_batch: sort workspace"); return FASTEGNN_E_INVALID; }
+  e = rocprim::radix_sort_pairs(p, need, keys, keys_s, vals, vals_s, (size_t)E, 0, end_bit, st);   // stable: ties keep edge order
+  if (e != hipSuccess) { set_error("cutoff_edges_batch: sort failed"); return FASTEGNN_E_LAUNCH; }
+  hipLaunchKernelGGL(batch_take_kernel, dim3(cdiv(keep_total, 256)), dim3(256), 0, st, edge_index, dist, (const int32_t *)vals_s,
+                     edge_ptr, keep_ptr, B, E, keep_total, edge_index_out, dist_out);
+  return check_launch("cutoff_edges_batch");
 }
 
 int fastegnn_nbody_cutoff_edges(const float *loc, int32_t S, int32_t n, int32_t k, int64_t *edge_index, float *dist,

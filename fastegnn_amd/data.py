@@ -10,7 +10,8 @@
 * ``NBodySystemDataset`` -- reader for the ``.npy`` files of ``datasets/nbody/datagen``
   (``datasets/nbody/dataset.py:44-113``), pinned by tests/golden/dataset_nbody5.npz.
 * ``Simulation`` -- reader for the Water-3D ``.h5`` files (``datasets/simulation/dataset.py:46-101``);
-  needs ``h5py`` and builds the radius graph on the GPU through the C-ABI (graphs.py).
+  needs ``h5py`` and builds the radius graph on the GPU through the C-ABI (graphs.py); ``water3d_batch`` and
+  ``frames_per_call`` build the graphs of several frames in one device call.
 * ``DataLoader`` -- ``batch_size`` / ``shuffle`` / ``drop_last`` iteration over frames (``main_nbody.py:93-96``).
 
 All processing is vectorised over the systems of a file and runs on the device the caller names.
@@ -184,6 +185,50 @@ def water3d_frame(loc_0, vel_0, loc_t, node_type, virtual_channels, radius=0.035
                  _loc_mean(loc_0, int(virtual_channels)))
 
 
+def _water3d_batch_edges(clouds, radius, cutoff_rate, rotation):
+    """The shared front of ``water3d_batch`` and ``Simulation(frames_per_call > 1)``: rotates every cloud
+    ``(loc_0, vel_0, loc_t)`` as ``water3d_frame`` does (a callable ``rotation`` is called once per cloud, in order) and builds
+    all their graphs with the two batched calls.  Returns (rotated clouds, host ptr list, edge_index with global ids, dist,
+    host edge_ptr list of the kept edges)."""
+    from .graphs import _radius_graph_batch, cutoff_edges_batch, keep_ptr_of
+    if rotation is not None:
+        rotated = []
+        for loc_0, vel_0, loc_t in clouds:
+            R = torch.as_tensor(rotation() if callable(rotation) else rotation).to(loc_0.device, torch.float32)
+            rotated.append((loc_0 @ R, vel_0 @ R, loc_t @ R))
+        clouds = rotated
+    ptr = [0]
+    for loc_0, _, _ in clouds:
+        ptr.append(ptr[-1] + loc_0.size(0))
+    ei, dist, edge_ptr, edge_ptr_host = _radius_graph_batch(torch.cat([c[0] for c in clouds], 0), ptr, radius)
+    ei, dist, _ = cutoff_edges_batch(ei, dist, edge_ptr, cutoff_rate, edge_ptr_host=edge_ptr_host)
+    return clouds, ptr, ei, dist, keep_ptr_of(edge_ptr_host, cutoff_rate)
+
+
+def water3d_batch(loc_0, vel_0, loc_t, node_type, ptr, virtual_channels, radius=0.035, cutoff_rate=0.0, rotation=None) -> Batch:
+    """``collate([water3d_frame(...) for every cloud])`` with the graphs of all clouds built in one device call
+    (graphs.radius_graph_batch / cutoff_edges_batch: one host read-back for the batch).  The node tensors hold B clouds back
+    to back, ``ptr`` (a list or an int64 tensor [B+1]; on the host it costs no read-back) their node ranges; every cloud must
+    hold at least one point.  Node features and ``loc_mean`` are computed per cloud by the expressions of the per-frame path,
+    so the result is bit-equal to it; a callable ``rotation`` is called once per cloud."""
+    ptr = [int(v) for v in torch.as_tensor(ptr).tolist()]
+    if len(ptr) < 2 or ptr[0] != 0 or ptr[-1] != loc_0.size(0) or any(a >= b for a, b in zip(ptr, ptr[1:])):
+        raise ValueError("water3d_batch: ptr must be 0 = ptr[0] < ... < ptr[B] = N")
+    dev, spans = loc_0.device, list(zip(ptr, ptr[1:]))
+    clouds, _, ei, dist, _ = _water3d_batch_edges([(loc_0[s:e], vel_0[s:e], loc_t[s:e]) for s, e in spans], radius, cutoff_rate,
+                                                  rotation)
+    counts = torch.tensor([e - s for s, e in spans], dtype=torch.int64)
+    out = {"loc_0": torch.cat([c[0] for c in clouds], 0), "loc_t": torch.cat([c[2] for c in clouds], 0),
+           "vel_0": torch.cat([c[1] for c in clouds], 0),
+           "node_feat": torch.cat([_node_feat(c[1], node_type[s:e]) for c, (s, e) in zip(clouds, spans)], 0),
+           "node_attr": torch.cat([node_type[s:e] for s, e in spans], 0),
+           "edge_attr": dist.unsqueeze(-1), "edge_index": ei,
+           "loc_mean": torch.cat([_loc_mean(c[0], int(virtual_channels)) for c in clouds], 0),
+           "batch": torch.repeat_interleave(torch.arange(len(spans), dtype=torch.int64), counts).to(dev),
+           "ptr": torch.tensor(ptr, dtype=torch.int64).to(dev)}
+    return Batch(**out)
+
+
 def read_trajectories(directory: str, partition: str):
     """Yields ``(key, position [T,n,3], particle_type [n])`` of every trajectory of a partition, in file order.
 
@@ -225,15 +270,20 @@ class Simulation:
     frames per trajectory with the unseeded ``random.randint(0, 250)`` (``:58``) and shuffles the frames
     (``:31``); here both come from ``seed``.  Per frame: ``vel_0 = pos[f+1] - pos[f]``, target
     ``pos[f + delta_t]``, edges = radius graph (r = 0.035, no self loops) reduced to the shortest
-    ``1 - cutoff_rate`` fraction, built on the GPU (graphs.radius_graph / graphs.cutoff_edges)."""
+    ``1 - cutoff_rate`` fraction, built on the GPU (graphs.radius_graph / graphs.cutoff_edges).
+    ``frames_per_call`` = k > 1 builds the graphs of up to k consecutive drawn frames of a trajectory in one batched call
+    (graphs.radius_graph_batch / cutoff_edges_batch: one read-back per call, not per frame); the frames are the same."""
 
     RADIUS = 0.035
     FRAMES_PER_TRAJECTORY = 15
 
     def __init__(self, dataset_name, data_dir, virtual_channels, partition="train", max_samples=1e8, delta_t=15,
-                 cutoff_rate=0.0, device="cuda", rotation=None, seed=0, radius=None):
+                 cutoff_rate=0.0, device="cuda", rotation=None, seed=0, radius=None, frames_per_call=1):
         self.virtual_channels, self.cutoff_rate, self.delta_t = int(virtual_channels), float(cutoff_rate), int(delta_t)
         self.radius = self.RADIUS if radius is None else float(radius)
+        frames_per_call = int(frames_per_call)
+        if frames_per_call < 1:
+            raise ValueError("Simulation: frames_per_call must be at least 1")
         rng = np.random.default_rng(seed)
         self.data: List[Frame] = []
         self.frames: List[tuple] = []      # (trajectory key, start frame) of every sample, in the order drawn
@@ -243,17 +293,33 @@ class Simulation:
             pos = torch.from_numpy(np.asarray(position)).float()
             n_frames = min(self.FRAMES_PER_TRAJECTORY, max_samples - len(self.data))
             last = min(250, pos.size(0) - 1 - max(1, self.delta_t))
-            for fr in rng.integers(0, last + 1, size=max(n_frames, 0)):
-                fr = int(fr)
-                self.frames.append((key, fr))
-                self.data.append(water3d_frame(pos[fr].to(device), (pos[fr + 1] - pos[fr]).to(device),
-                                               pos[fr + self.delta_t].to(device), ptype.to(device),
-                                               self.virtual_channels, self.radius, self.cutoff_rate, rotation))
+            drawn = rng.integers(0, last + 1, size=max(n_frames, 0))
+            if frames_per_call == 1:
+                for fr in drawn:
+                    fr = int(fr)
+                    self.frames.append((key, fr))
+                    self.data.append(water3d_frame(pos[fr].to(device), (pos[fr + 1] - pos[fr]).to(device),
+                                                   pos[fr + self.delta_t].to(device), ptype.to(device),
+                                                   self.virtual_channels, self.radius, self.cutoff_rate, rotation))
+            else:
+                for at in range(0, len(drawn), frames_per_call):
+                    group = [int(fr) for fr in drawn[at:at + frames_per_call]]
+                    self.frames.extend((key, fr) for fr in group)
+                    self.data.extend(self._frames_of(pos, ptype.to(device), group, device, rotation))
             if len(self.data) >= max_samples:
                 break
         order = rng.permutation(len(self.data))
         self.data = [self.data[i] for i in order]
         self.frames = [self.frames[i] for i in order]
+
+    def _frames_of(self, pos, ptype, group, device, rotation) -> List[Frame]:
+        """The frames of the start frames ``group`` of one trajectory, their edges from one batched build: the global edge
+        list is cut at the per-graph offsets and the node offset taken off the ids; the rest is ``water3d_frame``'s."""
+        clouds = [(pos[fr].to(device), (pos[fr + 1] - pos[fr]).to(device), pos[fr + self.delta_t].to(device)) for fr in group]
+        clouds, ptr, ei, dist, keep = _water3d_batch_edges(clouds, self.radius, self.cutoff_rate, rotation)
+        return [Frame(ei[:, a:b] - off, dist[a:b].clone().unsqueeze(-1), loc_0, loc_t, vel_0, _node_feat(vel_0, ptype), ptype,
+                      _loc_mean(loc_0, self.virtual_channels))
+                for (loc_0, vel_0, loc_t), off, a, b in zip(clouds, ptr, keep, keep[1:])]
 
     def __len__(self) -> int:
         return len(self.data)

@@ -524,6 +524,39 @@ size_t fastegnn_cutoff_tmp_bytes(int64_t E);
 int fastegnn_cutoff_edges(const int64_t *edge_index, const float *dist, int64_t E, int64_t keep, int64_t *edge_index_out,
                           float *dist_out, void *tmp, size_t tmp_bytes, void *stream);
 
+/* The same two steps for B ragged point clouds in one call (additive at this revision).  loc [N,3] holds the clouds back to
+ * back, ptr int64 [B+1] (device) their node ranges: 0 = ptr[0] <= ... <= ptr[B] = N.  Every cloud gets its own bounding box and
+ * cell grid by the single-cloud rule (cell edge max(r, extent / 255), at most 256 cells per axis), so its edges -- and the
+ * decision at the r boundary -- are those of fastegnn_radius_graph_* on that cloud alone, with global node ids: the list is
+ * grouped by graph, inside a graph by centre in ascending id with neighbours ascending; no edge joins two graphs.  The
+ * workspace (fastegnn_radius_graph_batch_ws_bytes(N, B) bytes) grows with N and B only: the points of a graph are ordered by
+ * cell id inside its own range of ONE radix sort on the key (graph, cell id), and a run of cells is found by binary search in
+ * that range -- there is no table over the 2^24 possible cells.
+ * _count runs everything up to the per-node offsets and copies edge_ptr [B+1] (edge_ptr[b] = first edge of graph b,
+ * edge_ptr[B] = E) and one status word to the host: the call's single synchronisation.  A ptr that is not as above sets
+ * the status word and the call returns FASTEGNN_E_INVALID (the kernels clamp every range to [0, N], so nothing is indexed
+ * outside loc).  _fill writes edge_index int64 [2,E], dist [E] and the device copy edge_ptr [B+1]; it reads nothing back.
+ * N == 0 or B == 0: FASTEGNN_OK with every count zero, nothing launched.
+ * FASTEGNN_E_INVALID before any device call for: a null pointer that would be used, N < 0, B < 0, r <= 0, a workspace below
+ * the size above, n_edges < 0 or >= 2^31. */
+size_t fastegnn_radius_graph_batch_ws_bytes(int32_t N, int32_t B);
+int fastegnn_radius_graph_batch_count(const float *loc, const int64_t *ptr, int32_t N, int32_t B, float r, void *ws,
+                                      size_t ws_bytes, int64_t *edge_ptr_host /* [B+1] */, void *stream);
+int fastegnn_radius_graph_batch_fill(const float *loc, const int64_t *ptr, int32_t N, int32_t B, float r, void *ws,
+                                     size_t ws_bytes, int64_t n_edges, int64_t *edge_index, float *dist,
+                                     int64_t *edge_ptr /* device [B+1] */, void *stream);
+/* Segmented cutoff: of the edges edge_ptr[b] .. edge_ptr[b+1] of graph b keep the keep_ptr[b+1] - keep_ptr[b] shortest, in
+ * ascending length, equal lengths in their input order (one stable radix sort on the key (graph, distance bits)); graph b's
+ * edges land at keep_ptr[b] .. of the outputs (edge_index_out int64 [2,keep_total], dist_out [keep_total], may be null).
+ * edge_ptr and keep_ptr are device arrays [B+1] of prefix sums with edge_ptr[B] == E, keep_ptr[B] == keep_total and
+ * keep_b <= E_b.  Reads nothing back.  tmp: fastegnn_cutoff_batch_tmp_bytes(E, B) bytes.  keep_total == 0 or B == 0 launches
+ * nothing.  FASTEGNN_E_INVALID before any device call for: B < 0, E < 0, E >= 2^31, keep_total < 0 or > E, a null pointer
+ * that would be used, tmp below the size above. */
+size_t fastegnn_cutoff_batch_tmp_bytes(int64_t E, int32_t B);
+int fastegnn_cutoff_edges_batch(const int64_t *edge_index, const float *dist, const int64_t *edge_ptr, const int64_t *keep_ptr,
+                                int32_t B, int64_t E, int64_t keep_total, int64_t *edge_index_out, float *dist_out, void *tmp,
+                                size_t tmp_bytes, void *stream);
+
 /* N-body systems (datasets/nbody/dataset.py:102-113): for each of S systems of n <= 128 particles (loc [S,n,3]) the k
  * shortest ordered pairs (i, j != i) of the complete graph in ascending length (fp32 distance, each operation rounded
  * separately; equal lengths in ascending i*n+j): edge_index int64 [S,2,k] (particle ids within the system), dist [S,k]. */
