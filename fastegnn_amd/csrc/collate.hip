@@ -1,0 +1,295 @@
+// Mini-batch assembly from a packed, device-resident dataset (fastegnn_amd/data.py: PackedDataset / PackedLoader): what
+// data.collate does with B slices, eight torch.cat calls and two host-to-device copies, as TWO launches whose count does not
+// depend on B.
+//   plan    one workgroup: the batch's exclusive node and edge offsets [B+1] from the B frame ids and the packed tables' offsets
+//   gather  one launch over every output table: each table is a run of contiguous per-frame segments, so the batch is a
+//           segmented copy -- flat output element -> frame (bounded binary search in the batch offsets) -> source address.
+// Segment starts are not 16-byte aligned (rows are 3, 2 or 1 floats wide), so every access is one element per lane (4 bytes for
+// the float tables, 8 for edge_index and batch): consecutive lanes read and write consecutive addresses inside a segment.  64-bit
+// indices, no atomics, nothing read outside [src_ptr[id], src_ptr[id+1]) of a frame: ids are clamped to [0, n_frames) in the
+// kernels and an element whose offset does not fall inside its frame's source segment is skipped.
+#include "kernels.h"
+
+namespace fe {
+
+constexpr int CL_PLAN_THREADS = 1024;
+constexpr int CL_THREADS = 256;
+constexpr int CL_UNROLL = 8;                        // elements per thread and tile: that many loads in flight before the stores
+constexpr int CL_TILE = CL_THREADS * CL_UNROLL;
+constexpr int CL_MAX_JOBS = FASTEGNN_COLLATE_TABLES + 2;   // the float tables, the two rows of edge_index, batch
+constexpr int CL_MAX_BLOCKS = 2048;                 // beyond that the workgroups stride over the tiles
+
+enum { CL_NODE = 0, CL_EDGE = 1, CL_FRAME = 2 };    // what a table's rows are counted in
+enum { CL_COPY32 = 0, CL_INDEX64 = 1, CL_BATCH64 = 2 };
+
+struct ClJob {
+  const void *src;
+  void *dst;
+  long long n;         // output elements
+  long long tile0;     // first tile of the job
+  long long src_rows;  // rows of the source table (nothing is read at or beyond it)
+  int width, kind, op;
+};
+struct ClJobs {
+  ClJob job[CL_MAX_JOBS];
+  long long n_tiles;
+  int n_jobs;
+};
+struct ClPtrs {
+  const int64_t *ids;
+  const int64_t *src[2];   // the packed tables' node / edge offsets [n_frames + 1]
+  const int64_t *out[2];   // the batch's node / edge offsets [B + 1]
+  int B, n_frames;
+};
+
+__device__ __forceinline__ long long clamp_id(long long id, int n_frames) {
+  return id < 0 ? 0 : (id >= n_frames ? (long long)n_frames - 1 : id);
+}
+
+// ---- plan: exclusive scans of the frames' node and edge counts, 1024 frames per round with a running carry ----
+__global__ __launch_bounds__(CL_PLAN_THREADS) void collate_plan_kernel(const int64_t *__restrict__ ids, int B,
+                                                                        const int64_t *__restrict__ src_node_ptr,
+                                                                        const int64_t *__restrict__ src_edge_ptr, int n_frames,
+                                                                        int64_t *__restrict__ node_ptr_out,
+                                                                        int64_t *__restrict__ edge_ptr_out) {
+  __shared__ long long wsum[2][CL_PLAN_THREADS / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  long long carry[2] = {0, 0};   // the same in every thread
+  for (int base = 0; base < B; base += CL_PLAN_THREADS) {
+    const int i = base + t;
+    long long c[2] = {0, 0};
+    if (i < B) {
+      const long long id = clamp_id(ids[i], n_frames);
+      c[0] = src_node_ptr[id + 1] - src_node_ptr[id];
+      c[1] = src_edge_ptr[id + 1] - src_edge_ptr[id];
+      c[0] = c[0] < 0 ? 0 : c[0];
+      c[1] = c[1] < 0 ? 0 : c[1];
+    }
+    long long s[2] = {c[0], c[1]};   // inclusive scan inside the wave
+    for (int off = 1; off < 64; off <<= 1)
+      for (int k = 0; k < 2; ++k) {
+        const long long v = __shfl_up(s[k], off);
+        if (lane >= off) s[k] += v;
+      }
+    if (lane == 63) {
+      wsum[0][wave] = s[0];
+      wsum[1][wave] = s[1];
+    }
+    __syncthreads();
+    long long before[2] = {0, 0}, total[2] = {0, 0};
+    for (int w = 0; w < CL_PLAN_THREADS / 64; ++w)
+      for (int k = 0; k < 2; ++k) {
+        const long long v = wsum[k][w];
+        if (w < wave) before[k] += v;
+        total[k] += v;
+      }
+    if (i < B) {
+      node_ptr_out[i] = carry[0] + before[0] + s[0] - c[0];
+      edge_ptr_out[i] = carry[1] + before[1] + s[1] - c[1];
+    }
+    carry[0] += total[0];
+    carry[1] += total[1];
+    __syncthreads();   // wsum is rewritten by the next round
+  }
+  if (t == 0) {
+    node_ptr_out[B] = carry[0];
+    edge_ptr_out[B] = carry[1];
+  }
+}
+
+// ---- gather ----
+// largest f in [lo, hi] with ptr[f] * w <= e (ptr[lo] * w <= e is the caller's; a frame without rows shares its offset with the
+// next one, which this rule skips)
+__device__ __forceinline__ int find_frame(const int64_t *__restrict__ ptr, int lo, int hi, long long e, long long w) {
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (ptr[mid] * w <= e) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+struct ClSeg {   // frame f of the batch in one table: its first output element and its source segment, in elements
+  long long out0, src0, len, node0;
+};
+__device__ __forceinline__ ClSeg load_seg(const ClPtrs &P, int kind, int f, long long w) {
+  const long long id = clamp_id(P.ids[f], P.n_frames);
+  const long long s0 = P.src[kind][id], s1 = P.src[kind][id + 1];
+  ClSeg g;
+  g.out0 = P.out[kind][f] * w;
+  g.src0 = s0 * w;
+  g.len = (s1 - s0) * w;
+  g.node0 = P.out[CL_NODE][f];
+  return g;
+}
+
+// One tile of one table.  UNIFORM: the whole tile lies in frame flo (its segment data is the same for every lane and is loaded
+// once); otherwise every element finds its frame in [flo, fhi].
+template <int OP, bool UNIFORM>
+__device__ __forceinline__ void gather_tile(const ClJob &jb, const ClPtrs &P, long long e0, long long e1, int flo, int fhi) {
+  const long long w = jb.width, src_end = jb.src_rows * w;
+  long long src_at[CL_UNROLL], add[CL_UNROLL];
+  ClSeg g0 = {};
+  if (UNIFORM) g0 = load_seg(P, jb.kind, flo, w);
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) {
+    const long long e = e0 + u * CL_THREADS + threadIdx.x;
+    src_at[u] = -1;
+    add[u] = 0;
+    if (e < e1) {
+      int f = flo;
+      ClSeg g = g0;
+      if (!UNIFORM) {
+        f = find_frame(P.out[jb.kind], flo, fhi, e, w);
+        g = load_seg(P, jb.kind, f, w);
+      }
+      const long long local = e - g.out0;
+      if (local >= 0 && local < g.len && g.src0 >= 0 && g.src0 + local < src_end) {
+        src_at[u] = g.src0 + local;
+        add[u] = OP == CL_BATCH64 ? (long long)f : g.node0;
+      }
+    }
+  }
+  if (OP == CL_COPY32) {
+    const unsigned *__restrict__ src = (const unsigned *)jb.src;
+    unsigned *__restrict__ dst = (unsigned *)jb.dst;
+    unsigned v[CL_UNROLL];
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) v[u] = src_at[u] >= 0 ? src[src_at[u]] : 0u;
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u)
+      if (src_at[u] >= 0) dst[e0 + u * CL_THREADS + threadIdx.x] = v[u];
+  } else if (OP == CL_INDEX64) {
+    const long long *__restrict__ src = (const long long *)jb.src;
+    long long *__restrict__ dst = (long long *)jb.dst;
+    long long v[CL_UNROLL];
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) v[u] = src_at[u] >= 0 ? src[src_at[u]] : 0;
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u)
+      if (src_at[u] >= 0) dst[e0 + u * CL_THREADS + threadIdx.x] = v[u] + add[u];
+  } else {
+    long long *__restrict__ dst = (long long *)jb.dst;
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u)
+      if (src_at[u] >= 0) dst[e0 + u * CL_THREADS + threadIdx.x] = add[u];
+  }
+}
+
+// loc_mean: one row of `width` floats per frame on both sides, so the frame is a division
+__device__ __forceinline__ void gather_tile_frames(const ClJob &jb, const ClPtrs &P, long long e0, long long e1) {
+  const long long w = jb.width;
+  const float *__restrict__ src = (const float *)jb.src;
+  float *__restrict__ dst = (float *)jb.dst;
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) {
+    const long long e = e0 + u * CL_THREADS + threadIdx.x;
+    if (e < e1) {
+      const long long f = e / w;
+      const long long id = clamp_id(P.ids[f], P.n_frames);
+      if (id < jb.src_rows) dst[e] = src[id * w + (e - f * w)];
+    }
+  }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void collate_gather_kernel(const ClJobs J, const ClPtrs P) {
+  for (long long tile = blockIdx.x; tile < J.n_tiles; tile += gridDim.x) {
+    int j = 0;
+    for (int k = 1; k < J.n_jobs; ++k)
+      if (tile >= J.job[k].tile0) j = k;
+    const ClJob &jb = J.job[j];
+    const long long e0 = (tile - jb.tile0) * CL_TILE;
+    const long long e1 = e0 + CL_TILE < jb.n ? e0 + CL_TILE : jb.n;
+    if (jb.kind == CL_FRAME) {
+      gather_tile_frames(jb, P, e0, e1);
+      continue;
+    }
+    const int64_t *__restrict__ po = P.out[jb.kind];
+    const int flo = find_frame(po, 0, P.B - 1, e0, jb.width);
+    const int fhi = find_frame(po, flo, P.B - 1, e1 - 1, jb.width);
+    if (flo == fhi) {
+      if (jb.op == CL_COPY32) gather_tile<CL_COPY32, true>(jb, P, e0, e1, flo, fhi);
+      else if (jb.op == CL_INDEX64) gather_tile<CL_INDEX64, true>(jb, P, e0, e1, flo, fhi);
+      else gather_tile<CL_BATCH64, true>(jb, P, e0, e1, flo, fhi);
+    } else {
+      if (jb.op == CL_COPY32) gather_tile<CL_COPY32, false>(jb, P, e0, e1, flo, fhi);
+      else if (jb.op == CL_INDEX64) gather_tile<CL_INDEX64, false>(jb, P, e0, e1, flo, fhi);
+      else gather_tile<CL_BATCH64, false>(jb, P, e0, e1, flo, fhi);
+    }
+  }
+}
+
+static void add_job(ClJobs &J, const void *src, void *dst, long long n, long long src_rows, int width, int kind, int op) {
+  if (n <= 0) return;   // an empty table (a batch without edges) takes no tile
+  ClJob &jb = J.job[J.n_jobs++];
+  jb.src = src;
+  jb.dst = dst;
+  jb.n = n;
+  jb.tile0 = J.n_tiles;
+  jb.src_rows = src_rows;
+  jb.width = width;
+  jb.kind = kind;
+  jb.op = op;
+  J.n_tiles += (n + CL_TILE - 1) / CL_TILE;
+}
+
+}  // namespace fe
+
+using namespace fe;
+
+extern "C" {
+
+int fastegnn_collate_plan(const int64_t *ids, int32_t B, const int64_t *src_node_ptr, const int64_t *src_edge_ptr,
+                          int32_t n_frames, int64_t *node_ptr_out, int64_t *edge_ptr_out, void *stream) {
+  FE_REQUIRE(B >= 0, "collate_plan: B < 0");
+  FE_REQUIRE(n_frames >= 1, "collate_plan: the packed dataset holds no frame");
+  FE_REQUIRE(node_ptr_out && edge_ptr_out, "collate_plan: null output");
+  FE_REQUIRE(B == 0 || (ids && src_node_ptr && src_edge_ptr), "collate_plan: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope _ps(K_MISC, st);
+  hipLaunchKernelGGL(collate_plan_kernel, dim3(1), dim3(CL_PLAN_THREADS), 0, st, ids, B, src_node_ptr, src_edge_ptr, n_frames,
+                     node_ptr_out, edge_ptr_out);
+  return check_launch("collate_plan");
+}
+
+int fastegnn_collate_gather(const int64_t *ids, int32_t B, const int64_t *src_node_ptr, const int64_t *src_edge_ptr,
+                            int32_t n_frames, int64_t src_nodes, int64_t src_edges, const int64_t *node_ptr_out,
+                            const int64_t *edge_ptr_out, int64_t n_nodes_out, int64_t n_edges_out, const void *const *src_tables,
+                            void *const *dst_tables, const int32_t *widths, int64_t *batch_out, void *stream) {
+  FE_REQUIRE(B >= 0, "collate_gather: B < 0");
+  FE_REQUIRE(n_frames >= 1, "collate_gather: the packed dataset holds no frame");
+  FE_REQUIRE(src_nodes >= 0 && src_edges >= 0 && n_nodes_out >= 0 && n_edges_out >= 0, "collate_gather: negative size");
+  if (B == 0) return FASTEGNN_OK;
+  FE_REQUIRE(ids && src_node_ptr && src_edge_ptr && node_ptr_out && edge_ptr_out && src_tables && dst_tables && widths,
+             "collate_gather: null pointer");
+  ClJobs J = {};
+  for (int t = 0; t < FASTEGNN_COLLATE_TABLES - 1; ++t) {
+    FE_REQUIRE(widths[t] >= 0 && widths[t] <= (1 << 20), "collate_gather: row width out of range (0 .. 2^20)");
+    const int kind = t < FASTEGNN_COLLATE_EDGE_ATTR ? CL_NODE : (t == FASTEGNN_COLLATE_EDGE_ATTR ? CL_EDGE : CL_FRAME);
+    const long long rows = kind == CL_NODE ? n_nodes_out : (kind == CL_EDGE ? n_edges_out : (long long)B);
+    const long long src_rows = kind == CL_NODE ? src_nodes : (kind == CL_EDGE ? src_edges : (long long)n_frames);
+    FE_REQUIRE(rows * widths[t] == 0 || (src_tables[t] && dst_tables[t]), "collate_gather: null table");
+    add_job(J, src_tables[t], dst_tables[t], rows * widths[t], src_rows, widths[t], kind, CL_COPY32);
+  }
+  const int64_t *ei_src = (const int64_t *)src_tables[FASTEGNN_COLLATE_EDGE_INDEX];
+  int64_t *ei_dst = (int64_t *)dst_tables[FASTEGNN_COLLATE_EDGE_INDEX];
+  FE_REQUIRE(n_edges_out == 0 || (ei_src && ei_dst), "collate_gather: null edge_index");
+  for (int r = 0; r < 2 && n_edges_out > 0; ++r)   // row r of [2,E] on both sides
+    add_job(J, ei_src + (size_t)r * src_edges, ei_dst + (size_t)r * n_edges_out, n_edges_out, src_edges, 1, CL_EDGE, CL_INDEX64);
+  if (batch_out) add_job(J, nullptr, batch_out, n_nodes_out, src_nodes, 1, CL_NODE, CL_BATCH64);
+  if (J.n_tiles == 0) return FASTEGNN_OK;   // nothing to write: no launch on an empty grid
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope _ps(K_MISC, st);
+  ClPtrs P;
+  P.ids = ids;
+  P.src[0] = src_node_ptr;
+  P.src[1] = src_edge_ptr;
+  P.out[0] = node_ptr_out;
+  P.out[1] = edge_ptr_out;
+  P.B = B;
+  P.n_frames = n_frames;
+  const int grid = (int)(J.n_tiles < CL_MAX_BLOCKS ? J.n_tiles : CL_MAX_BLOCKS);
+  hipLaunchKernelGGL(collate_gather_kernel, dim3(grid), dim3(CL_THREADS), 0, st, J, P);
+  return check_launch("collate_gather");
+}
+
+}  // extern "C"

@@ -13,6 +13,8 @@
   needs ``h5py`` and builds the radius graph on the GPU through the C-ABI (graphs.py); ``water3d_batch`` and
   ``frames_per_call`` build the graphs of several frames in one device call.
 * ``DataLoader`` -- ``batch_size`` / ``shuffle`` / ``drop_last`` iteration over frames (``main_nbody.py:93-96``).
+* ``PackedDataset`` / ``PackedLoader`` -- the same batches from a dataset packed once into one device table per field: a batch
+  is two kernel launches (csrc/collate.hip) whatever its size, with no host-to-device copy and no synchronisation.
 
 All processing is vectorised over the systems of a file and runs on the device the caller names.
 """
@@ -347,3 +349,164 @@ class DataLoader:
         for i in range(len(self)):
             b = collate([self.dataset[j] for j in order[i * self.batch_size:(i + 1) * self.batch_size]])
             yield b.to(self.device) if self.device is not None else b
+
+
+# ---- device-resident packed datasets: a batch is two launches, whatever B is (csrc/collate.hip) ----
+_PACK_KEYS = _NODE_KEYS + ("edge_attr", "loc_mean", "edge_index")   # FASTEGNN_COLLATE_* order (include/fastegnn_hip.h)
+_NO_CPU = "fastegnn_amd: PackedDataset.batch needs device-resident tables (there is no CPU fallback)"
+
+
+class HipCollateOps:
+    """The two device calls of a packed batch on libfastegnn_hip.so (the product path).  tests/packed_ref.py restates them in
+    torch so that tests/test_packed_cpu.py can drive the loader's orchestration without a GPU (the ``wide.HipOps`` precedent)."""
+
+    @staticmethod
+    def plan(ids, src_node_ptr, src_edge_ptr, node_ptr_out, edge_ptr_out) -> None:
+        """node_ptr_out / edge_ptr_out [B+1] <- exclusive prefix sums of the node / edge counts of the frames ``ids``"""
+        if not ids.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        from . import _lib as K
+        from .model import _stream
+        K.check(K.lib().fastegnn_collate_plan(K.ptr(ids), ids.numel(), K.ptr(src_node_ptr), K.ptr(src_edge_ptr),
+                                              src_node_ptr.numel() - 1, K.ptr(node_ptr_out), K.ptr(edge_ptr_out),
+                                              _stream(ids.device)), "fastegnn_collate_plan")
+
+    @staticmethod
+    def gather(ids, src_node_ptr, src_edge_ptr, node_ptr_out, edge_ptr_out, src_tables, dst_tables, batch_out) -> None:
+        """every tensor of the batch in one launch; ``src_tables`` / ``dst_tables``: the eight tensors in ``_PACK_KEYS`` order"""
+        if not ids.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        import ctypes as C
+        from . import _lib as K
+        from .model import _stream
+        n = len(_PACK_KEYS)
+        src = (C.c_void_p * n)(*[t.data_ptr() or None for t in src_tables])
+        dst = (C.c_void_p * n)(*[t.data_ptr() or None for t in dst_tables])
+        widths = (C.c_int32 * (n - 1))(*[math.prod(t.shape[1:]) for t in src_tables[:n - 1]])
+        K.check(K.lib().fastegnn_collate_gather(K.ptr(ids), ids.numel(), K.ptr(src_node_ptr), K.ptr(src_edge_ptr),
+                                                src_node_ptr.numel() - 1, src_tables[0].size(0), src_tables[5].size(0),
+                                                K.ptr(node_ptr_out), K.ptr(edge_ptr_out), dst_tables[0].size(0),
+                                                dst_tables[5].size(0), src, dst, widths, K.ptr(batch_out), _stream(ids.device)),
+                "fastegnn_collate_gather")
+
+
+_COLLATE_OPS = HipCollateOps
+
+
+class PackedDataset:
+    """The frames of a dataset (``NBodySystemDataset(...)``, ``Simulation(...)``, a list of ``Frame``) concatenated ONCE into one
+    table per field on ``device`` (default: where the first frame lives), ``edge_index`` with the frames' LOCAL node ids.
+    ``node_ptr`` / ``edge_ptr`` [n+1] are the prefix sums of the node / edge counts, on the device; ``node_ptr_host`` /
+    ``edge_ptr_host`` the same as host int64 arrays, from which every output size is computed -- nothing is ever read back.
+    ``packed[i]`` is a ``Frame`` of views into the tables, so a packed dataset can stand wherever a dataset does.
+    ``batch(ids)`` is ``collate([packed[i] for i in ids])`` bit for bit, assembled by two kernel launches."""
+
+    def __init__(self, frames, device=None):
+        n = len(frames)
+        if n == 0:
+            raise ValueError("PackedDataset: empty sequence of frames")
+        fl = [frames[i] for i in range(n)]
+        first = fl[0]
+        for i, f in enumerate(fl):
+            for k in _PACK_KEYS:
+                t, want = getattr(f, k), torch.int64 if k == "edge_index" else torch.float32
+                if t.dtype != want:
+                    raise ValueError(f"PackedDataset: frame {i}: {k} is {t.dtype}, expected {want}")
+                if k != "edge_index" and (t.dim() != first[k].dim() or t.shape[1:] != first[k].shape[1:]):
+                    raise ValueError(f"PackedDataset: frame {i}: {k} has shape {list(t.shape)}, frame 0 has {list(first[k].shape)}")
+            if any(getattr(f, k).dim() != 2 or getattr(f, k).size(0) != f.num_nodes for k in _NODE_KEYS):
+                raise ValueError(f"PackedDataset: frame {i}: the node tensors must be [n, width] with one n")
+            if f.loc_mean.dim() != 3 or f.loc_mean.size(0) != 1 or f.loc_mean.size(1) != 3:
+                raise ValueError(f"PackedDataset: frame {i}: loc_mean must be [1,3,C], got {list(f.loc_mean.shape)}")
+            if f.edge_index.dim() != 2 or f.edge_index.size(0) != 2 or f.edge_attr.dim() != 2 or \
+                    f.edge_attr.size(0) != f.edge_index.size(1):
+                raise ValueError(f"PackedDataset: frame {i}: edge_index must be [2,E] and edge_attr [E, width]")
+        self.device = torch.device(device) if device is not None else first.node_feat.device
+        self.tables = {k: torch.cat([getattr(f, k) for f in fl], 1 if k == "edge_index" else 0).to(self.device).contiguous()
+                       for k in _PACK_KEYS}
+        self.node_ptr_host = np.concatenate([[0], np.cumsum([f.num_nodes for f in fl], dtype=np.int64)]).astype(np.int64)
+        self.edge_ptr_host = np.concatenate([[0], np.cumsum([f.edge_index.size(1) for f in fl], dtype=np.int64)]).astype(np.int64)
+        self.node_ptr = torch.from_numpy(self.node_ptr_host).to(self.device)
+        self.edge_ptr = torch.from_numpy(self.edge_ptr_host).to(self.device)
+        self._node_cnt, self._edge_cnt = np.diff(self.node_ptr_host), np.diff(self.edge_ptr_host)
+
+    def __len__(self) -> int:
+        return self.node_ptr_host.size - 1
+
+    def __getitem__(self, i: int) -> Frame:
+        n = len(self)
+        i = int(i)
+        if not -n <= i < n:
+            raise IndexError(f"PackedDataset: frame {i} of {n}")
+        i %= n
+        a, b = int(self.node_ptr_host[i]), int(self.node_ptr_host[i + 1])
+        ea, eb = int(self.edge_ptr_host[i]), int(self.edge_ptr_host[i + 1])
+        T = self.tables
+        return Frame(T["edge_index"][:, ea:eb], T["edge_attr"][ea:eb], *[T[k][a:b] for k in _NODE_KEYS], T["loc_mean"][i:i + 1])
+
+    def _upload(self, ids: torch.Tensor) -> torch.Tensor:
+        """host int64 ids -> device, without a synchronisation: through a FRESH pinned buffer and a non-blocking copy (the
+        caching host allocator hands a pinned block out again only after the copies queued from it have completed, so no
+        buffer is rewritten under a queued copy)."""
+        if self.device.type != "cuda":
+            return ids.to(self.device)
+        staging = torch.empty(ids.numel(), dtype=torch.int64, pin_memory=True)
+        staging.copy_(ids)
+        return staging.to(self.device, non_blocking=True)
+
+    def _assemble(self, ids_dev: torch.Tensor, ids_host: np.ndarray) -> Batch:
+        """the batch of the frames ``ids_dev`` (device int64 [B]); ``ids_host``: the same ids on the host, already validated"""
+        B, dev, T = int(ids_host.size), self.device, self.tables
+        n_nodes, n_edges = int(self._node_cnt[ids_host].sum()), int(self._edge_cnt[ids_host].sum())
+        out = {k: torch.empty((n_nodes,) + T[k].shape[1:], dtype=torch.float32, device=dev) for k in _NODE_KEYS}
+        out["edge_attr"] = torch.empty((n_edges,) + T["edge_attr"].shape[1:], dtype=torch.float32, device=dev)
+        out["edge_index"] = torch.empty((2, n_edges), dtype=torch.int64, device=dev)
+        out["loc_mean"] = torch.empty((B,) + T["loc_mean"].shape[1:], dtype=torch.float32, device=dev)
+        out["batch"] = torch.empty(n_nodes, dtype=torch.int64, device=dev)
+        out["ptr"] = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        edge_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        _COLLATE_OPS.plan(ids_dev, self.node_ptr, self.edge_ptr, out["ptr"], edge_ptr)
+        _COLLATE_OPS.gather(ids_dev, self.node_ptr, self.edge_ptr, out["ptr"], edge_ptr, [T[k] for k in _PACK_KEYS],
+                            [out[k] for k in _PACK_KEYS], out["batch"])
+        return Batch(**out)
+
+    def batch(self, ids) -> Batch:
+        """``collate([self[i] for i in ids])``: same keys in the same order, every tensor fresh and contiguous.  ``ids``: a host
+        sequence, numpy array or CPU tensor of frame numbers in ``[0, len(self))`` (any order, repeats allowed), checked on the
+        host: an id outside raises IndexError.  Two kernel launches and the upload of ``ids``; nothing is read back."""
+        if isinstance(ids, torch.Tensor):
+            if ids.is_cuda:
+                raise ValueError("PackedDataset.batch: ids must live on the host")
+            ids = ids.numpy()
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or ids.size == 0:
+            raise ValueError("PackedDataset.batch: ids must be a non-empty 1-D sequence")
+        if ids.dtype.kind not in "iu":
+            raise ValueError(f"PackedDataset.batch: ids must be integers, got {ids.dtype}")
+        ids = ids.astype(np.int64)
+        if ids.min() < 0 or ids.max() >= len(self):
+            raise IndexError(f"PackedDataset.batch: ids span [{ids.min()}, {ids.max()}] but there are {len(self)} frames")
+        return self._assemble(self._upload(torch.from_numpy(ids)), ids)
+
+
+class PackedLoader:
+    """``DataLoader`` over a ``PackedDataset``: same batching, same ``torch.randperm(n, generator=...)`` order (equal generators
+    give the same batches in the same order).  The epoch's order is uploaded ONCE, through pinned memory with a non-blocking
+    copy; every batch hands the kernels a slice of that device tensor, so a batch is two launches and no copy."""
+
+    def __init__(self, packed: PackedDataset, batch_size=1, shuffle=False, drop_last=False,
+                 generator: Optional[torch.Generator] = None):
+        self.packed, self.batch_size, self.shuffle, self.drop_last = packed, int(batch_size), shuffle, drop_last
+        self.generator = generator
+
+    def __len__(self) -> int:
+        n = len(self.packed)
+        return n // self.batch_size if self.drop_last else math.ceil(n / self.batch_size)
+
+    def __iter__(self) -> Iterator[Batch]:
+        n = len(self.packed)
+        order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
+        ids_dev, order_host = self.packed._upload(order), order.numpy()
+        for i in range(len(self)):
+            a, b = i * self.batch_size, min((i + 1) * self.batch_size, n)
+            yield self.packed._assemble(ids_dev[a:b], order_host[a:b])

@@ -563,6 +563,45 @@ int fastegnn_cutoff_edges_batch(const int64_t *edge_index, const float *dist, co
 int fastegnn_nbody_cutoff_edges(const float *loc, int32_t S, int32_t n, int32_t k, int64_t *edge_index, float *dist,
                                 void *stream);
 
+/* ---- mini-batch assembly from a packed dataset (the collate of torch_geometric.loader.DataLoader, main_nbody.py:93-96) ----
+ * ADDITIVE exports, found by symbol: FASTEGNN_ABI_VERSION stays 108.
+ * A packed dataset holds every field of its n_frames graphs in ONE device table per field, frame after frame, with the prefix
+ * sums src_node_ptr / src_edge_ptr (int64 [n_frames + 1], device) of the frames' node and edge counts; edge_index is int64
+ * [2, src_edges] with node ids LOCAL to the frame.  A batch is the B frames ids[0 .. B) (int64, device; any order, repeats
+ * allowed) and costs two launches whatever B is; neither call reads anything back, synchronises or allocates.
+ *   _plan    node_ptr_out / edge_ptr_out int64 [B+1]: exclusive prefix sums of the chosen frames' node / edge counts (node_ptr_out
+ *            is the batch's `ptr`).  One workgroup, 1024 frames per round with a running carry: any B.
+ *   _gather  every output of the batch in one launch, a segmented copy (flat output element -> frame by binary search in the
+ *            batch offsets -> source address; one element per lane, 64-bit indices, no atomics):
+ *              dst_tables[t] [n_out, widths[t]] fp32 for t = LOC_0 .. EDGE_ATTR  (n_out = n_nodes_out, for EDGE_ATTR n_edges_out)
+ *              dst_tables[LOC_MEAN] [B, widths[LOC_MEAN]] fp32   (row ids[i] of the source's [n_frames, widths[LOC_MEAN]])
+ *              dst_tables[EDGE_INDEX] int64 [2, n_edges_out] = the frames' local ids + node_ptr_out[frame]
+ *              batch_out int64 [n_nodes_out] = position of the node's frame in the batch (may be null: not written)
+ *            src_tables / dst_tables: HOST arrays of FASTEGNN_COLLATE_TABLES device pointers in the order below, widths: HOST
+ *            int32 [FASTEGNN_COLLATE_TABLES - 1] floats per row.  src_nodes / src_edges: rows of the packed node / edge tables;
+ *            n_nodes_out / n_edges_out: the batch's totals, which the caller knows from its host copy of the counts and has sized
+ *            the outputs by -- they must equal node_ptr_out[B] / edge_ptr_out[B].
+ * The kernels clamp every id to [0, n_frames) and skip an element whose offset does not fall inside its frame's source segment,
+ * so nothing is read outside [src_ptr[id], src_ptr[id+1]) or beyond the packed tables, and nothing is written beyond the totals
+ * given, whatever the device arrays hold.  A table without output elements (a batch without edges) takes no part; when every
+ * table is empty, or B == 0, _gather launches nothing.  FASTEGNN_E_INVALID before any launch for: B < 0, n_frames < 1, a
+ * negative size, a width outside 0 .. 2^20, a null pointer that would be used. */
+#define FASTEGNN_COLLATE_LOC_0 0
+#define FASTEGNN_COLLATE_LOC_T 1
+#define FASTEGNN_COLLATE_VEL_0 2
+#define FASTEGNN_COLLATE_NODE_FEAT 3
+#define FASTEGNN_COLLATE_NODE_ATTR 4
+#define FASTEGNN_COLLATE_EDGE_ATTR 5
+#define FASTEGNN_COLLATE_LOC_MEAN 6
+#define FASTEGNN_COLLATE_EDGE_INDEX 7
+#define FASTEGNN_COLLATE_TABLES 8
+int fastegnn_collate_plan(const int64_t *ids, int32_t B, const int64_t *src_node_ptr, const int64_t *src_edge_ptr,
+                          int32_t n_frames, int64_t *node_ptr_out, int64_t *edge_ptr_out, void *stream);
+int fastegnn_collate_gather(const int64_t *ids, int32_t B, const int64_t *src_node_ptr, const int64_t *src_edge_ptr,
+                            int32_t n_frames, int64_t src_nodes, int64_t src_edges, const int64_t *node_ptr_out,
+                            const int64_t *edge_ptr_out, int64_t n_nodes_out, int64_t n_edges_out, const void *const *src_tables,
+                            void *const *dst_tables, const int32_t *widths, int64_t *batch_out, void *stream);
+
 /* ---- exchange steps of the sharded path (the reference has no distributed code) ----
  * RCCL collectives behind the C ABI: every call is enqueued on `stream` (ordered with the stage kernels, capturable
  * into a HIP graph) and returns at once.  RCCL is bound at run time (dlopen; FASTEGNN_E_NODEVICE when absent).

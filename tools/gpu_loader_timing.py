@@ -1,0 +1,175 @@
+"""Times one epoch of data.DataLoader (per batch: B slices, eight torch.cat calls, two copies from pageable memory) against one
+epoch of data.PackedLoader (per batch: two launches of csrc/collate.hip) over the SAME device-resident frames on one GPU.  Host
+wall clock around an epoch that ends in one device synchronise; both loaders warmed up, then alternated in one process; the
+median of EPOCHS epochs with min, max and inter-quartile range (the box's epoch-to-epoch spread).  Each shape twice: the loader
+alone (every batch is dropped as soon as it is built), and the loader with train_step on every batch.  Three shapes from seeds:
+cfg1-like and cfg2-like N-body frames at batch size 100, Water-3D-like clouds (r = 0.035 graphs of graphs.radius_graph_batch)
+at batch size 20.  The batches of the two loaders are compared with torch.equal first.  Prints what profiles/packed_loader.txt
+holds.
+
+    python tools/gpu_loader_timing.py [output file]
+"""
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import fastegnn_amd  # noqa: E402
+from fastegnn_amd import data as D  # noqa: E402
+from fastegnn_amd.graphs import radius_graph_batch  # noqa: E402
+from fastegnn_amd.train import FusedAdam, MMDSampler, train_step  # noqa: E402
+
+EPOCHS, WARM, C = 15, 2, 3
+
+
+def _frame(loc_0, ei, gen):
+    n = loc_0.size(0)
+    vel = torch.randn(n, 3, generator=gen) * 0.01
+    kind = torch.randint(0, 2, (n, 1), generator=gen).float() + 1.0
+    ea = (loc_0[ei[0]] - loc_0[ei[1]]).norm(dim=1, keepdim=True)
+    return D.Frame(ei, ea, loc_0, loc_0 + 10 * vel, vel, D._node_feat(vel, kind), kind, D._loc_mean(loc_0, C))
+
+
+def nbody_frames(n_frames, n, seed):
+    gen = torch.Generator().manual_seed(seed)
+    ij = torch.tensor([(i, j) for i in range(n) for j in range(n) if i != j], dtype=torch.int64).t().contiguous()
+    return [_frame(torch.randn(n, 3, generator=gen), ij, gen).to("cuda") for _ in range(n_frames)]
+
+
+def water_frames(n_frames, seed, per_call=15):
+    gen = torch.Generator().manual_seed(seed)
+    frames = []
+    for at in range(0, n_frames, per_call):
+        sizes = torch.randint(7600, 8401, (min(per_call, n_frames - at),), generator=gen).tolist()
+        clouds = [torch.rand(n, 3, generator=gen) * 0.42 for n in sizes]
+        ptr = [0]
+        for n in sizes:
+            ptr.append(ptr[-1] + n)
+        ei, _, ep = radius_graph_batch(torch.cat(clouds, 0).cuda(), ptr, 0.035)
+        ei, ep = ei.cpu(), ep.tolist()
+        frames += [_frame(c, ei[:, a:b] - o, gen).to("cuda") for c, o, a, b in zip(clouds, ptr, ep, ep[1:])]
+    return frames
+
+
+def gather_kernel_us(packed, ids, runs=20):
+    """the gather launch of one batch by itself: outputs allocated once, the plan run once, then `runs` launches under the
+    library's per-launch HIP events (fastegnn_profile_enable) -> (mean microseconds, launches counted)"""
+    from fastegnn_amd import _lib as K
+    b = packed.batch(ids)
+    ids_dev = ids.cuda()
+    edge_ptr = torch.empty_like(b["ptr"])
+    ops, T = D._COLLATE_OPS, packed.tables
+    ops.plan(ids_dev, packed.node_ptr, packed.edge_ptr, b["ptr"], edge_ptr)
+    args = (ids_dev, packed.node_ptr, packed.edge_ptr, b["ptr"], edge_ptr, [T[k] for k in D._PACK_KEYS],
+            [b[k] for k in D._PACK_KEYS], b["batch"])
+    for _ in range(3):
+        ops.gather(*args)
+    torch.cuda.synchronize()
+    K.lib().fastegnn_profile_enable(1)
+    K.profile_collect()
+    for _ in range(runs):
+        ops.gather(*args)
+    K.lib().fastegnn_profile_enable(0)
+    ms, n = K.profile_collect()["misc"]
+    return ms / n * 1e3, n
+
+
+def copy_us(nbytes, runs=20):
+    """a plain device-to-device copy of nbytes (torch's copy kernel), device events around `runs` of them -> microseconds each"""
+    src = torch.rand(nbytes // 4, device="cuda")
+    dst = torch.empty_like(src)
+    for _ in range(3):
+        dst.copy_(src)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(runs):
+        dst.copy_(src)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / runs * 1e3
+
+
+def epoch_times(loaders, body):
+    """alternates the loaders: EPOCHS timed epochs each after WARM warm-ups -> {name: [seconds]}"""
+    ts = {name: [] for name, _ in loaders}
+    for it in range(WARM + EPOCHS):
+        for name, loader in loaders:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for batch in loader:
+                body(batch)
+            torch.cuda.synchronize()
+            if it >= WARM:
+                ts[name].append(time.perf_counter() - t0)
+    return ts
+
+
+def line(name, ts, n_batches):
+    q = statistics.quantiles(ts, n=4)
+    med = statistics.median(ts)
+    return (f"    {name:<12} median {med * 1e3:9.3f} ms per epoch ({med / n_batches * 1e6:9.1f} us per batch)   min {min(ts) * 1e3:9.3f}  "
+            f"max {max(ts) * 1e3:9.3f}  IQR {(q[2] - q[0]) * 1e3:8.3f} ms   of {len(ts)} epochs after {WARM} warm-ups")
+
+
+def main():
+    out = [f"device: {torch.cuda.get_device_name(0)}; host wall clock around one epoch ending in one device synchronise; "
+           f"the two loaders alternate in one process"]
+    shapes = [("cfg1-like: 2000 frames x 5 nodes x 20 edges, batch size 100", lambda: nbody_frames(2000, 5, 1), 100),
+              ("cfg2-like: 500 frames x 100 nodes x 9900 edges, batch size 100", lambda: nbody_frames(500, 100, 2), 100),
+              ("Water-3D-like: 60 frames x 7600..8400 nodes, r = 0.035 in a 0.42^3 box, batch size 20", lambda: water_frames(60, 3), 20)]
+    for name, make, bs in shapes:
+        frames = make()
+        packed = D.PackedDataset(frames)
+        old = D.DataLoader(frames, batch_size=bs, shuffle=True, generator=torch.Generator().manual_seed(9))
+        new = D.PackedLoader(packed, batch_size=bs, shuffle=True, generator=torch.Generator().manual_seed(9))
+        same = all(list(a.keys()) == list(b.keys()) and all(torch.equal(a[k], b[k]) for k in a.keys()) for a, b in zip(new, old))
+        nb = len(new)
+        first = next(iter(new))
+        bytes_moved = 2 * sum(first[k].numel() * first[k].element_size() for k in first.keys())
+        out.append(f"{name}")
+        out.append(f"  {nb} batches per epoch; first batch: {first.num_nodes} nodes, {first['edge_index'].size(1)} edges, "
+                   f"{bytes_moved / 1e6:.2f} MB read + written; PackedLoader batches equal DataLoader's (torch.equal, every key): {same}")
+        # the gather kernel by itself on the first batch (device events around the two launches, outputs allocated outside)
+        ids = torch.randperm(len(frames), generator=torch.Generator().manual_seed(4))[:bs]
+        ev = []
+        for _ in range(23):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            packed.batch(ids)
+            b.record()
+            b.synchronize()
+            ev.append(a.elapsed_time(b))
+        ev = ev[3:]
+        out.append(f"  PackedDataset.batch (id upload + plan + gather, device events): median {statistics.median(ev) * 1e3:.1f} us "
+                   f"(min {min(ev) * 1e3:.1f}, max {max(ev) * 1e3:.1f}) of 20 after 3 warm-ups = "
+                   f"{bytes_moved / statistics.median(ev) / 1e6:.0f} GB/s read + written at the median")
+        us, n = gather_kernel_us(packed, ids)
+        out.append(f"  the gather launch alone (HIP events around the launch, the library's profiler): {us:.1f} us mean of {n} = "
+                   f"{bytes_moved / us / 1e3:.0f} GB/s read + written;  a torch copy_ of the same bytes: "
+                   f"{bytes_moved / copy_us(bytes_moved // 2) / 1e3:.0f} GB/s")
+        loaders = [("DataLoader", old), ("PackedLoader", new)]
+        out.append("  loader alone:")
+        ts = epoch_times(loaders, lambda batch: None)
+        out += [line(k, ts[k], nb) for k, _ in loaders]
+        model = fastegnn_amd.FastEGNN(node_feat_nf=2, node_attr_nf=0, edge_attr_nf=2, hidden_nf=64, virtual_channels=C,
+                                      device="cuda", n_layers=4)
+        opt = FusedAdam(model.parameters(), lr=5e-4, weight_decay=1e-12)
+        smp = MMDSampler(0)
+        out.append("  loader + train_step (FastEGNN hidden 64, 4 layers, C = 3, device-side MMD sample):")
+        ts = epoch_times(loaders, lambda batch: train_step(model, opt, batch, None, sigma=1.0, weight=0.01, sampler=smp,
+                                                           num_sample=3 * C))
+        out += [line(k, ts[k], nb) for k, _ in loaders]
+        del frames, packed, old, new, model, opt
+        torch.cuda.empty_cache()
+    text = "\n".join(out)
+    print(text)
+    if len(sys.argv) > 1:
+        with open(sys.argv[1], "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
