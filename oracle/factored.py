@@ -258,9 +258,10 @@ def edge_fwd(w: LayerW, cfg: Config, csr: Csr, P, Q, x, ea, x_src=None):
     return aggm, aggx
 
 
-def edge_bwd(w: LayerW, cfg: Config, G, L: str, csr: Csr, P, Q, x, ea, g_aggm, g_aggx, x_src=None):
+def edge_bwd(w: LayerW, cfg: Config, G, L: str, csr: Csr, P, Q, x, ea, g_aggm, g_aggx, x_src=None, extra=None):
     """returns g_P [N,H], g_Q [N,H], g_x [N,3] (row side + col side); with a source table (x_src given)
-    returns g_P, g_Q [n_src,H], (g_x_row [N,3], g_x_src [n_src,3])."""
+    returns g_P, g_Q [n_src,H], (g_x_row [N,3], g_x_src [n_src,3]).  extra: a dict that receives g_pre [E,H], the
+    gradient at the first pre-activation of every sorted edge (d loss / d edge_attr = g_pre @ We)."""
     k = _edge_recompute(w, cfg, csr, P, Q, x, ea, x_src)
     N = csr.n
     idg = csr.inv_deg[csr.row]
@@ -287,6 +288,8 @@ def edge_bwd(w: LayerW, cfg: Config, G, L: str, csr: Csr, P, Q, x, ea, g_aggm, g
     G[f"{L}.edge_mlp.2.bias"] += g_mp.sum(0)
     G[f"{L}.edge_mlp.2.weight"] += R(g_mp).T @ R(k["t"])
     g_pre = (R(g_mp) @ R(w.W2)) * dsilu(k["pre"])
+    if extra is not None:
+        extra["g_pre"] = g_pre
     dW1 = G[f"{L}.edge_mlp.0.weight"]
     dW1[:, 2 * H] += g_pre.T @ k["r"]
     dW1[:, 2 * H + 1:] += g_pre.T @ ea
@@ -349,8 +352,9 @@ def virt_fwd(w: LayerW, cfg: Config, h, A, Bc, x, vel, Z, batch, aggm, aggx, sve
 
 
 def virt_bwd(w: LayerW, cfg: Config, G, L: str, h, A, Bc, x, vel, Z, batch, aggm, gravity,
-             g_hn, g_xn, g_poolV, g_poolX, node_attr=None):
-    """returns dict(g_h, g_x, g_A, g_aggm, g_aggx, g_svel, g_sgrav, g_Bc, g_Z, g_vel[, via svel])."""
+             g_hn, g_xn, g_poolV, g_poolX, node_attr=None, extra=None):
+    """returns dict(g_h, g_x, g_A, g_aggm, g_aggx, g_svel, g_sgrav, g_Bc, g_Z, g_vel[, via svel]).  extra: a dict that
+    receives g_np [N,H], the gradient at node_mlp's pre-activation (d loss / d node_attr = g_np @ W3d)."""
     B, C = Z.size(0), Z.size(2)
     N = h.size(0)
     k = _virt_recompute(w, cfg, A, Bc, x, Z, batch)
@@ -365,6 +369,8 @@ def virt_bwd(w: LayerW, cfg: Config, G, L: str, h, A, Bc, x, vel, Z, batch, aggm
     G[f"{L}.node_mlp.2.bias"] += g_out.sum(0)
     G[f"{L}.node_mlp.2.weight"] += R(g_out).T @ R(t3)
     g_np = (R(g_out) @ R(w.W4)) * dsilu(nodepre)
+    if extra is not None:
+        extra["g_np"] = g_np
     dW3 = G[f"{L}.node_mlp.0.weight"]
     G[f"{L}.node_mlp.0.bias"] += g_np.sum(0)
     dW3[:, :H] += R(g_np).T @ R(h)

@@ -199,6 +199,17 @@ GRAD_EXCEPTIONS = [
      "2.16e-6 .. 2.36e-6 on another; the CPU re-association 1.94e-6).  Seven runs on one box take three values -- 4.29e-6 (3 x), 5.05e-6 (3 x), 6.18e-6 "
      "(once): the order in which the pools' atomics of four workgroups arrive -- against 2 x ref + 1e-6 = 4.58e-6; the f16x2 build 1.21e-6.  The row the "
      "bf16x3 build had here while it was the default (rounds 1-3: floor 2e-6 at a measured 4.67e-6) left with it in round 4"),
+    # The stage-level comparisons (tests/test_gpu_stages.py: one stage entry point, independent N(0,1) operands, case names "stage:<stage>:<shape>:
+    # <flags>:<build>"): 15 000 comparisons per pass over the four libraries, ONE kind beyond the plain rule, spread evenly over the rows of the
+    # buffer (no row or graph stands out: the per-row error quantiles sit at a constant multiple of the fp32 CPU evaluation's): the price of adding INTO a
+    # buffer that already holds a value -- measured minus that start value.  Floor = 1.5 x the largest excess over 2 x ref
+    (r"^stage:node_pre_backward:", r"^g_h$", 2.0, 1.7e-6,
+     "g_h += five 64-wide products (P, Q, A and the two scalar heads' first layers), all in ONE accumulator that starts from the g_h the virtual stage "
+     "left (here an N(0,1) draw, max 4): every one of the ~60 matrix-core accumulations of a bf16x3 product chain rounds at the magnitude of start + "
+     "partial sum, where the CPU evaluation forms each product on its own and adds five times.  Per-row error q50 / q90 / q99: 4.5e-7 / 6.6e-7 / 8.8e-7 "
+     "against the CPU's 1.0e-7 / 1.4e-7 / 1.9e-7 (681 rows).  Worst: 1.579e-6 vs ref 2.69e-7 (681 nodes, all flags) and 1.557e-6 vs ref 2.02e-7 (64 nodes, "
+     "gravity) = 1.04e-6 / 1.15e-6 over 2 x ref; bit-identical over four runs and on all four libraries (the kernel is the bf16x3 form in each); without "
+     "gravity (four products) 1.04e-6 vs 2.60e-7: inside the plain rule"),
 ]
 
 
