@@ -8,6 +8,9 @@
 // the float tables, 8 for edge_index and batch): consecutive lanes read and write consecutive addresses inside a segment.  64-bit
 // indices, no atomics, nothing read outside [src_ptr[id], src_ptr[id+1]) of a frame: ids are clamped to [0, n_frames) in the
 // kernels and an element whose offset does not fall inside its frame's source segment is skipped.
+//   graph   (optional, two more launches) the batch's SORTED index -- what fastegnn_build_csr would make of the batch's edge_index --
+//           from the frames' own sorted indices, kept in the packed dataset: the same segmented walk with an offset added to every
+//           integer, then csr.hip's chunk kernel on the assembled rowptr.  No sort, no atomics, no workspace.
 #include "kernels.h"
 
 namespace fe {
@@ -218,6 +221,98 @@ __global__ __launch_bounds__(CL_THREADS) void collate_gather_kernel(const ClJobs
   }
 }
 
+// ---- graph: the batch's sorted index from the frames' own (fastegnn_collate_graph) ----
+// The same segmented walk over int32 outputs.  CG_PTR: rowptr / cscptr, int64 positions in the packed edge table -> positions in the
+// batch's (minus the frame's first packed edge, plus its first edge in the batch); the job is one element longer than the batch has
+// nodes, and that last element is the edge total.  CG_NODE_ID: erow / col, frame-local node ids + the frame's first node.
+// CG_EDGE_ID: perm / csc_eid, frame-local edge positions + the frame's first edge.  CG_ZERO: rowptr / cscptr of a batch without edges.
+enum { CG_PTR = 3, CG_NODE_ID = 4, CG_EDGE_ID = 5, CG_ZERO = 6 };
+
+template <int OP>
+__device__ __forceinline__ long long graph_add(const ClPtrs &P, int f, const ClSeg &g) {
+  if (OP == CG_NODE_ID) return g.node0;
+  const long long eo = P.out[CL_EDGE][f];
+  return OP == CG_EDGE_ID ? eo : eo - P.src[CL_EDGE][clamp_id(P.ids[f], P.n_frames)];
+}
+
+template <int OP, bool UNIFORM>
+__device__ __forceinline__ void graph_tile(const ClJob &jb, const ClPtrs &P, long long e0, long long e1, int flo, int fhi,
+                                           long long n_edges_out) {
+  const long long n_seg = OP == CG_PTR ? jb.n - 1 : jb.n;   // elements that come from a frame's segment
+  long long src_at[CL_UNROLL], add[CL_UNROLL];
+  ClSeg g0 = {};
+  long long add0 = 0;
+  if (UNIFORM) {
+    g0 = load_seg(P, jb.kind, flo, 1);
+    add0 = graph_add<OP>(P, flo, g0);
+  }
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) {
+    const long long e = e0 + u * CL_THREADS + threadIdx.x;
+    src_at[u] = -1;
+    add[u] = 0;
+    if (e < e1 && e < n_seg) {
+      ClSeg g = g0;
+      long long a = add0;
+      if (!UNIFORM) {
+        const int f = find_frame(P.out[jb.kind], flo, fhi, e, 1);
+        g = load_seg(P, jb.kind, f, 1);
+        a = graph_add<OP>(P, f, g);
+      }
+      const long long local = e - g.out0;
+      if (local >= 0 && local < g.len && g.src0 >= 0 && g.src0 + local < jb.src_rows) {
+        src_at[u] = g.src0 + local;
+        add[u] = a;
+      }
+    }
+  }
+  int32_t *__restrict__ dst = (int32_t *)jb.dst;
+  long long v[CL_UNROLL];
+  if (OP == CG_PTR) {
+    const long long *__restrict__ src = (const long long *)jb.src;
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) v[u] = src_at[u] >= 0 ? src[src_at[u]] : 0;
+  } else {
+    const int32_t *__restrict__ src = (const int32_t *)jb.src;
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) v[u] = src_at[u] >= 0 ? (long long)src[src_at[u]] : 0;
+  }
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) {
+    const long long e = e0 + u * CL_THREADS + threadIdx.x;
+    if (src_at[u] >= 0) dst[e] = (int32_t)(v[u] + add[u]);
+    else if (OP == CG_PTR && e == n_seg && e < e1) dst[e] = (int32_t)n_edges_out;
+  }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void collate_graph_kernel(const ClJobs J, const ClPtrs P, const long long n_edges_out) {
+  for (long long tile = blockIdx.x; tile < J.n_tiles; tile += gridDim.x) {
+    int j = 0;
+    for (int k = 1; k < J.n_jobs; ++k)
+      if (tile >= J.job[k].tile0) j = k;
+    const ClJob &jb = J.job[j];
+    const long long e0 = (tile - jb.tile0) * CL_TILE;
+    const long long e1 = e0 + CL_TILE < jb.n ? e0 + CL_TILE : jb.n;
+    if (jb.op == CG_ZERO || P.B == 0) {   // no edge anywhere: every offset is 0 (a batch of no frames holds that one element)
+      int32_t *__restrict__ dst = (int32_t *)jb.dst;
+      for (long long e = e0 + threadIdx.x; e < e1; e += CL_THREADS) dst[e] = 0;
+      continue;
+    }
+    const int64_t *__restrict__ po = P.out[jb.kind];
+    const int flo = find_frame(po, 0, P.B - 1, e0, 1);
+    const int fhi = find_frame(po, flo, P.B - 1, e1 - 1, 1);
+    if (flo == fhi) {
+      if (jb.op == CG_PTR) graph_tile<CG_PTR, true>(jb, P, e0, e1, flo, fhi, n_edges_out);
+      else if (jb.op == CG_NODE_ID) graph_tile<CG_NODE_ID, true>(jb, P, e0, e1, flo, fhi, n_edges_out);
+      else graph_tile<CG_EDGE_ID, true>(jb, P, e0, e1, flo, fhi, n_edges_out);
+    } else {
+      if (jb.op == CG_PTR) graph_tile<CG_PTR, false>(jb, P, e0, e1, flo, fhi, n_edges_out);
+      else if (jb.op == CG_NODE_ID) graph_tile<CG_NODE_ID, false>(jb, P, e0, e1, flo, fhi, n_edges_out);
+      else graph_tile<CG_EDGE_ID, false>(jb, P, e0, e1, flo, fhi, n_edges_out);
+    }
+  }
+}
+
 static void add_job(ClJobs &J, const void *src, void *dst, long long n, long long src_rows, int width, int kind, int op) {
   if (n <= 0) return;   // an empty table (a batch without edges) takes no tile
   ClJob &jb = J.job[J.n_jobs++];
@@ -290,6 +385,51 @@ int fastegnn_collate_gather(const int64_t *ids, int32_t B, const int64_t *src_no
   const int grid = (int)(J.n_tiles < CL_MAX_BLOCKS ? J.n_tiles : CL_MAX_BLOCKS);
   hipLaunchKernelGGL(collate_gather_kernel, dim3(grid), dim3(CL_THREADS), 0, st, J, P);
   return check_launch("collate_gather");
+}
+
+int fastegnn_collate_graph(const int64_t *ids, int32_t B, const int64_t *src_node_ptr, const int64_t *src_edge_ptr, int32_t n_frames,
+                           int64_t src_nodes, int64_t src_edges, const int64_t *node_ptr_out, const int64_t *edge_ptr_out,
+                           int64_t n_nodes_out, int64_t n_edges_out, const int64_t *g_rowptr, const int32_t *g_erow,
+                           const int32_t *g_col, const int32_t *g_perm, const int64_t *g_cscptr, const int32_t *g_csc_eid,
+                           int32_t *rowptr, int32_t *erow, int32_t *col, int32_t *perm, int32_t *cscptr, int32_t *csc_eid,
+                           int32_t *chunk_row, int32_t *n_chunks, void *stream) {
+  FE_REQUIRE(B >= 0, "collate_graph: B < 0");
+  FE_REQUIRE(n_frames >= 1, "collate_graph: the packed dataset holds no frame");
+  FE_REQUIRE(src_nodes >= 0 && src_edges >= 0 && n_nodes_out >= 0 && n_edges_out >= 0, "collate_graph: negative size");
+  FE_REQUIRE(n_nodes_out < 0x7fffffffll && n_edges_out <= 0x7fffffffll, "collate_graph: the batch exceeds the int32 sizes of build_csr");
+  FE_REQUIRE(B > 0 || (n_nodes_out == 0 && n_edges_out == 0), "collate_graph: nodes or edges in a batch of no frames");
+  FE_REQUIRE(rowptr && chunk_row && n_chunks, "collate_graph: null output");
+  FE_REQUIRE((cscptr == nullptr) == (csc_eid == nullptr), "collate_graph: cscptr and csc_eid are given or omitted together");
+  const bool want_csc = cscptr != nullptr;
+  FE_REQUIRE((g_cscptr == nullptr) == (g_csc_eid == nullptr), "collate_graph: g_cscptr and g_csc_eid are given or omitted together");
+  FE_REQUIRE(B == 0 || (ids && src_node_ptr && src_edge_ptr && node_ptr_out && edge_ptr_out), "collate_graph: null pointer");
+  FE_REQUIRE(n_edges_out == 0 || (g_rowptr && g_erow && g_col && g_perm && erow && col && perm), "collate_graph: null pointer");
+  FE_REQUIRE(n_edges_out == 0 || !want_csc || g_cscptr, "collate_graph: a col-keyed index is asked for but the packed tables hold none");
+  const long long np1 = n_nodes_out + 1;
+  const int ptr_op = n_edges_out > 0 ? CG_PTR : CG_ZERO;
+  ClJobs J = {};
+  add_job(J, g_rowptr, rowptr, np1, src_nodes, 1, CL_NODE, ptr_op);
+  if (want_csc) add_job(J, g_cscptr, cscptr, np1, src_nodes, 1, CL_NODE, ptr_op);
+  add_job(J, g_erow, erow, n_edges_out, src_edges, 1, CL_EDGE, CG_NODE_ID);
+  add_job(J, g_col, col, n_edges_out, src_edges, 1, CL_EDGE, CG_NODE_ID);
+  add_job(J, g_perm, perm, n_edges_out, src_edges, 1, CL_EDGE, CG_EDGE_ID);
+  if (want_csc) add_job(J, g_csc_eid, csc_eid, n_edges_out, src_edges, 1, CL_EDGE, CG_EDGE_ID);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope _ps(K_MISC, st);
+  ClPtrs P;
+  P.ids = ids;
+  P.src[0] = src_node_ptr;
+  P.src[1] = src_edge_ptr;
+  P.out[0] = node_ptr_out;
+  P.out[1] = edge_ptr_out;
+  P.B = B;
+  P.n_frames = n_frames;
+  const int grid = (int)(J.n_tiles < CL_MAX_BLOCKS ? J.n_tiles : CL_MAX_BLOCKS);   // rowptr is never empty: at least one tile
+  hipLaunchKernelGGL(collate_graph_kernel, dim3(grid), dim3(CL_THREADS), 0, st, J, P, (long long)n_edges_out);
+  const int nch = csr_chunk_count((int)n_edges_out);
+  *n_chunks = nch;
+  launch_chunk_rows(rowptr, (int)n_nodes_out, nch, chunk_row, st);
+  return check_launch("collate_graph");
 }
 
 }  // extern "C"

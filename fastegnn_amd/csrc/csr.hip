@@ -50,6 +50,10 @@ __global__ void chunk_kernel(const int32_t *rowptr, int n_rows, int n_chunks, in
   }
   chunk_row[k] = lo;
 }
+int csr_chunk_count(int E) { return E / CHUNK_EDGES + 1; }
+void launch_chunk_rows(const int32_t *rowptr, int n_rows, int n_chunks, int32_t *chunk_row, hipStream_t st) {
+  hipLaunchKernelGGL(chunk_kernel, dim3(cdiv(n_chunks + 1, 256)), dim3(256), 0, st, rowptr, n_rows, n_chunks, chunk_row);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The same index by COUNTING (round 6): graphs whose ids have few edges each -- radius graphs, the shards of one -- do not need the radix
@@ -274,7 +278,7 @@ int fastegnn_build_csr(const int64_t *edge_index, int32_t E, int32_t row_begin, 
   FE_REQUIRE(tmp_bytes >= fastegnn_csr_tmp_bytes(E, n_rows, n_src), "build_csr: tmp too small");
   hipStream_t st = (hipStream_t)stream;
   ProfScope _ps(K_CSR, st);
-  const int nch = E / CHUNK_EDGES + 1;
+  const int nch = csr_chunk_count(E);
   *n_chunks = nch;
   // by counting while an id has <= 64 edges on average and the edge list is short: the counting form costs ~25 us + 0.13 us per 1 000 edges
   // (two atomics per edge), the radix sorts ~107 us + 0.034 -- measured inside the step on one MI355X: 55 against 115 us at the 240 k edges of
@@ -322,7 +326,7 @@ int fastegnn_build_csr(const int64_t *edge_index, int32_t E, int32_t row_begin, 
     (void)hipMemsetAsync(rowptr, 0, (size_t)(n_rows + 1) * 4, st);
     if (want_csc) (void)hipMemsetAsync(cscptr, 0, (size_t)(n_src + 1) * 4, st);
   }
-  hipLaunchKernelGGL(chunk_kernel, dim3(cdiv(nch + 1, 256)), dim3(256), 0, st, rowptr, n_rows, nch, chunk_row);
+  launch_chunk_rows(rowptr, n_rows, nch, chunk_row, st);
   return check_launch("build_csr");
 }
 

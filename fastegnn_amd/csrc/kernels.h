@@ -88,6 +88,11 @@ int launch_dgrad_small(const float *G, long N, int kf, const float *W, int ldw, 
 int launch_wgrad_small(const float *G, int ldg, const float *F, int ldf, int kf, long M, float *dW, int lddw, int c0,
                        hipStream_t st);
 
+// csr.hip: the edge-balanced row chunks of a finished rowptr -- the last launch of fastegnn_build_csr, shared with
+// fastegnn_collate_graph (collate.hip), whose rowptr is assembled and not sorted.  chunk_row holds csr_chunk_count(E) + 1 ints.
+int csr_chunk_count(int E);
+void launch_chunk_rows(const int32_t *rowptr, int n_rows, int n_chunks, int32_t *chunk_row, hipStream_t st);
+
 // stage launchers
 int pack_weights(const fastegnn_layer_t *L, hipStream_t st);
 int pack_weights_all(const fastegnn_layer_t *const *layers, int n, hipStream_t st);

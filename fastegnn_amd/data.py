@@ -14,7 +14,9 @@
   ``frames_per_call`` build the graphs of several frames in one device call.
 * ``DataLoader`` -- ``batch_size`` / ``shuffle`` / ``drop_last`` iteration over frames (``main_nbody.py:93-96``).
 * ``PackedDataset`` / ``PackedLoader`` -- the same batches from a dataset packed once into one device table per field: a batch
-  is two kernel launches (csrc/collate.hip) whatever its size, with no host-to-device copy and no synchronisation.
+  is two kernel launches (csrc/collate.hip) whatever its size, with no host-to-device copy and no synchronisation.  With
+  ``graphs=...`` a batch also carries its ``SortedGraph``, assembled by two more launches from per-frame indices sorted once
+  (``PackedDataset.build_graphs``): the model then sorts nothing per batch.
 
 All processing is vectorised over the systems of a file and runs on the device the caller names.
 """
@@ -83,17 +85,20 @@ class Batch:
     def num_nodes(self) -> int:
         return self._t["batch"].numel()
 
+    # a packed batch may carry its sorted graph (key "graph", a model.SortedGraph: PackedLoader(graphs=...)); it is no tensor and
+    # passes through the three calls below as it is -- its arrays stay on the device they were assembled on
     def to(self, device, non_blocking: bool = False) -> "Batch":
-        return Batch(**{k: v.to(device, non_blocking=non_blocking) for k, v in self._t.items()})
+        return Batch(**{k: v.to(device, non_blocking=non_blocking) if isinstance(v, torch.Tensor) else v for k, v in self._t.items()})
 
     def detach(self) -> "Batch":
-        return Batch(**{k: v.detach() for k, v in self._t.items()})
+        return Batch(**{k: v.detach() if isinstance(v, torch.Tensor) else v for k, v in self._t.items()})
 
     def pin_memory(self) -> "Batch":
-        return Batch(**{k: v.pin_memory() for k, v in self._t.items()})
+        return Batch(**{k: v.pin_memory() if isinstance(v, torch.Tensor) else v for k, v in self._t.items()})
 
     def __repr__(self) -> str:
-        return "Batch(" + ", ".join(f"{k}={list(v.shape)}" for k, v in self._t.items()) + ")"
+        return "Batch(" + ", ".join(f"{k}={list(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}"
+                                    for k, v in self._t.items()) + ")"
 
 
 def collate(frames: Sequence[Frame]) -> Batch:
@@ -358,7 +363,8 @@ _NO_CPU = "fastegnn_amd: PackedDataset.batch needs device-resident tables (there
 
 class HipCollateOps:
     """The two device calls of a packed batch on libfastegnn_hip.so (the product path).  tests/packed_ref.py restates them in
-    torch so that tests/test_packed_cpu.py can drive the loader's orchestration without a GPU (the ``wide.HipOps`` precedent)."""
+    torch so that tests/test_packed_cpu.py can drive the loader's orchestration without a GPU (the ``wide.HipOps`` precedent).
+    ``sort`` and ``graph`` are the two calls behind a batch's sorted graph (tests/packed_graph_ref.py restates them likewise)."""
 
     @staticmethod
     def plan(ids, src_node_ptr, src_edge_ptr, node_ptr_out, edge_ptr_out) -> None:
@@ -389,8 +395,58 @@ class HipCollateOps:
                                                 dst_tables[5].size(0), src, dst, widths, K.ptr(batch_out), _stream(ids.device)),
                 "fastegnn_collate_gather")
 
+    @staticmethod
+    def sort(edge_index, n_nodes):
+        """packing time: (rowptr, erow, col, perm, cscptr, csc_eid) of one slab of frames, ``fastegnn_build_csr``'s own (int32, edge
+        arrays [E])"""
+        if not edge_index.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        from .model import SortedGraph
+        g, E = SortedGraph(edge_index, n_nodes, csc=True), edge_index.size(1)
+        return g.rowptr, g.erow[:E], g.col[:E], g.perm[:E], g.cscptr, g.csc_eid[:E]
+
+    @staticmethod
+    def graph(ids, src_node_ptr, src_edge_ptr, node_ptr_out, edge_ptr_out, n_nodes_out, n_edges_out, src_graph, dst_graph,
+              chunk_row) -> int:
+        """the batch's sorted index in two launches (fastegnn_collate_graph); ``src_graph``: the packed g_rowptr, g_erow, g_col,
+        g_perm, g_cscptr, g_csc_eid; ``dst_graph``: rowptr, erow, col, perm, cscptr, csc_eid (the last two None: no col-keyed
+        index).  Returns n_chunks, which is host arithmetic."""
+        if not ids.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        import ctypes as C
+        from . import _lib as K
+        from .model import _stream
+        nch = C.c_int32(0)
+        K.check(K.lib().fastegnn_collate_graph(K.ptr(ids), ids.numel(), K.ptr(src_node_ptr), K.ptr(src_edge_ptr),
+                                               src_node_ptr.numel() - 1, src_graph[0].numel() - 1, src_graph[1].numel(),
+                                               K.ptr(node_ptr_out), K.ptr(edge_ptr_out), n_nodes_out, n_edges_out,
+                                               *[K.ptr(t) for t in src_graph], *[K.ptr(t) for t in dst_graph], K.ptr(chunk_row),
+                                               C.byref(nch), _stream(ids.device)), "fastegnn_collate_graph")
+        return nch.value
+
 
 _COLLATE_OPS = HipCollateOps
+
+# PackedDataset.build_graphs sorts the frames in slabs of whole frames, each slab one fastegnn_build_csr call: a slab is closed before
+# it would exceed any of these (a single frame beyond them is a slab of its own).  Far inside the sorted graph's own limits below, so
+# that the sort workspace (28 bytes per edge) stays near a hundred megabytes.
+GRAPH_SLAB_NODES = 1 << 20
+GRAPH_SLAB_EDGES = 1 << 22
+GRAPH_SLAB_FRAMES = 1 << 16
+# the edge stages address their tables with 32-bit offsets (include/fastegnn_hip.h, fastegnn_build_csr): n * 68 and E * 8 below 2^30
+_GRAPH_MAX_NODES = (1 << 30) // 68
+_GRAPH_MAX_EDGES = (1 << 30) // 8 - 1
+_GRAPH_KEYS = ("g_rowptr", "g_erow", "g_col", "g_perm", "g_cscptr", "g_csc_eid")
+
+
+def _check_graphs(graphs) -> None:
+    if not (graphs is None or graphs in ("csr", "csr+csc") or callable(graphs)):
+        raise ValueError(f"fastegnn_amd: graphs must be None, 'csr', 'csr+csc' or a callable n_edges -> bool, got {graphs!r}")
+
+
+def _chunk_edges() -> int:
+    from . import _lib as K
+    return K.lib().fastegnn_chunk_edges()
 
 
 class PackedDataset:
@@ -429,6 +485,53 @@ class PackedDataset:
         self.node_ptr = torch.from_numpy(self.node_ptr_host).to(self.device)
         self.edge_ptr = torch.from_numpy(self.edge_ptr_host).to(self.device)
         self._node_cnt, self._edge_cnt = np.diff(self.node_ptr_host), np.diff(self.edge_ptr_host)
+        self.graph_tables = None   # the per-frame sorted indices: build_graphs(), only when a batch is asked for its graph
+
+    def build_graphs(self) -> "PackedDataset":
+        """Sorts every frame's graph ONCE, so that a batch's ``SortedGraph`` is assembled by a gather and no sort runs per batch.
+        The existing ``fastegnn_build_csr`` is run over slabs of whole frames (``GRAPH_SLAB_NODES`` / ``_EDGES`` / ``_FRAMES``), a slab
+        being one batch with global ids; its result is stored with ids and positions local to the frame (plain torch, one-off) in
+        ``graph_tables``: ``g_rowptr`` / ``g_cscptr`` int64 [nodes + 1], ``g_erow`` / ``g_col`` / ``g_perm`` / ``g_csc_eid`` int32 [edges]
+        (include/fastegnn_hip.h, fastegnn_collate_graph) -- 16 bytes per edge plus 16 per node of device memory.  A frame beyond
+        the sorted graph's own limits (15.7 M nodes, 134 M edges) raises ValueError.  Idempotent; returns self."""
+        if self.graph_tables is not None:
+            return self
+        n, dev = len(self), self.device
+        for f in range(n):
+            if self._node_cnt[f] > _GRAPH_MAX_NODES or self._edge_cnt[f] > _GRAPH_MAX_EDGES:
+                raise ValueError(f"PackedDataset.build_graphs: frame {f} has {self._node_cnt[f]} nodes and {self._edge_cnt[f]} edges; a "
+                                 f"sorted graph holds at most {_GRAPH_MAX_NODES} nodes and {_GRAPH_MAX_EDGES} edges")
+        cap_n, cap_e = min(GRAPH_SLAB_NODES, _GRAPH_MAX_NODES), min(GRAPH_SLAB_EDGES, _GRAPH_MAX_EDGES)
+        nodes, edges = int(self.node_ptr_host[-1]), int(self.edge_ptr_host[-1])
+        ptr64 = lambda: torch.empty(nodes + 1, dtype=torch.int64, device=dev)  # noqa: E731
+        idx32 = lambda: torch.empty(edges, dtype=torch.int32, device=dev)  # noqa: E731
+        G = dict(g_rowptr=ptr64(), g_erow=idx32(), g_col=idx32(), g_perm=idx32(), g_cscptr=ptr64(), g_csc_eid=idx32())
+        f0 = 0
+        while f0 < n:
+            f1 = f0 + 1   # a slab holds at least one frame
+            while f1 < n and f1 - f0 < GRAPH_SLAB_FRAMES and self.node_ptr_host[f1 + 1] - self.node_ptr_host[f0] <= cap_n \
+                    and self.edge_ptr_host[f1 + 1] - self.edge_ptr_host[f0] <= cap_e:
+                f1 += 1
+            n0, n1 = int(self.node_ptr_host[f0]), int(self.node_ptr_host[f1])
+            e0, e1 = int(self.edge_ptr_host[f0]), int(self.edge_ptr_host[f1])
+            # the frame of every edge of the slab: the stable sort by row keeps each frame's edges in the frame's own range of
+            # positions (frames own ascending node ranges), and so does the col-keyed order, so this holds for sorted positions too
+            frame_of = torch.repeat_interleave(torch.arange(f1 - f0, device=dev), self.edge_ptr[f0 + 1:f1 + 1] - self.edge_ptr[f0:f1],
+                                               output_size=e1 - e0)
+            node_off, edge_off = (self.node_ptr[f0:f1] - n0)[frame_of], (self.edge_ptr[f0:f1] - e0)[frame_of]
+            ei = (self.tables["edge_index"][:, e0:e1] + node_off).contiguous()
+            rowptr, erow, col, perm, cscptr, csc_eid = _COLLATE_OPS.sort(ei, n1 - n0)
+            G["g_rowptr"][n0:n1] = rowptr[:-1].long() + e0
+            G["g_cscptr"][n0:n1] = cscptr[:-1].long() + e0
+            G["g_erow"][e0:e1] = erow - node_off.int()
+            G["g_col"][e0:e1] = col - node_off.int()
+            G["g_perm"][e0:e1] = perm - edge_off.int()
+            G["g_csc_eid"][e0:e1] = csc_eid - edge_off.int()
+            f0 = f1
+        G["g_rowptr"][nodes] = edges
+        G["g_cscptr"][nodes] = edges
+        self.graph_tables = G
+        return self
 
     def __len__(self) -> int:
         return self.node_ptr_host.size - 1
@@ -454,7 +557,7 @@ class PackedDataset:
         staging.copy_(ids)
         return staging.to(self.device, non_blocking=True)
 
-    def _assemble(self, ids_dev: torch.Tensor, ids_host: np.ndarray) -> Batch:
+    def _assemble(self, ids_dev: torch.Tensor, ids_host: np.ndarray, graphs=None) -> Batch:
         """the batch of the frames ``ids_dev`` (device int64 [B]); ``ids_host``: the same ids on the host, already validated"""
         B, dev, T = int(ids_host.size), self.device, self.tables
         n_nodes, n_edges = int(self._node_cnt[ids_host].sum()), int(self._edge_cnt[ids_host].sum())
@@ -468,12 +571,32 @@ class PackedDataset:
         _COLLATE_OPS.plan(ids_dev, self.node_ptr, self.edge_ptr, out["ptr"], edge_ptr)
         _COLLATE_OPS.gather(ids_dev, self.node_ptr, self.edge_ptr, out["ptr"], edge_ptr, [T[k] for k in _PACK_KEYS],
                             [out[k] for k in _PACK_KEYS], out["batch"])
+        if graphs is not None:
+            out["graph"] = self._assemble_graph(ids_dev, out["ptr"], edge_ptr, n_nodes, n_edges, graphs)
         return Batch(**out)
 
-    def batch(self, ids) -> Batch:
+    def _assemble_graph(self, ids_dev, node_ptr_out, edge_ptr_out, n_nodes: int, n_edges: int, graphs):
+        """the batch's ``SortedGraph`` from the per-frame indices (two launches, sizes from the host counts: nothing is read back)"""
+        from .model import SortedGraph
+        csc = bool(graphs(n_edges)) if callable(graphs) else graphs == "csr+csc"
+        G = self.build_graphs().graph_tables
+        i32 = dict(dtype=torch.int32, device=self.device)
+        arr = [torch.empty(n_nodes + 1, **i32)] + [torch.empty(max(n_edges, 1), **i32) for _ in range(3)]   # rowptr, erow, col, perm
+        arr += [torch.empty(n_nodes + 1, **i32), torch.empty(max(n_edges, 1), **i32)] if csc else [None, None]
+        chunk_row = torch.empty(n_edges // _chunk_edges() + 2, **i32)   # fastegnn_chunk_rows(E)
+        n_chunks = _COLLATE_OPS.graph(ids_dev, self.node_ptr, self.edge_ptr, node_ptr_out, edge_ptr_out, n_nodes, n_edges,
+                                      [G[k] for k in _GRAPH_KEYS], arr, chunk_row)
+        return SortedGraph.from_arrays(*arr, chunk_row, n_chunks, n_nodes, n_nodes, n_edges)
+
+    def batch(self, ids, graphs=None) -> Batch:
         """``collate([self[i] for i in ids])``: same keys in the same order, every tensor fresh and contiguous.  ``ids``: a host
         sequence, numpy array or CPU tensor of frame numbers in ``[0, len(self))`` (any order, repeats allowed), checked on the
-        host: an id outside raises IndexError.  Two kernel launches and the upload of ``ids``; nothing is read back."""
+        host: an id outside raises IndexError.  Two kernel launches and the upload of ``ids``; nothing is read back.
+        ``graphs``: None (default) -- exactly that; ``"csr"`` / ``"csr+csc"`` / a callable ``n_edges -> bool`` (does this batch need the
+        col-keyed index?  e.g. ``model.deterministic_for``) -- the batch gains one key, ``"graph"``: the ``SortedGraph`` of its
+        ``edge_index``, element for element what the model would have sorted, assembled from indices sorted once
+        (``build_graphs``, run on first use) by two more launches.  Pass it to the model as ``edge_index=``."""
+        _check_graphs(graphs)
         if isinstance(ids, torch.Tensor):
             if ids.is_cuda:
                 raise ValueError("PackedDataset.batch: ids must live on the host")
@@ -486,18 +609,21 @@ class PackedDataset:
         ids = ids.astype(np.int64)
         if ids.min() < 0 or ids.max() >= len(self):
             raise IndexError(f"PackedDataset.batch: ids span [{ids.min()}, {ids.max()}] but there are {len(self)} frames")
-        return self._assemble(self._upload(torch.from_numpy(ids)), ids)
+        return self._assemble(self._upload(torch.from_numpy(ids)), ids, graphs)
 
 
 class PackedLoader:
     """``DataLoader`` over a ``PackedDataset``: same batching, same ``torch.randperm(n, generator=...)`` order (equal generators
     give the same batches in the same order).  The epoch's order is uploaded ONCE, through pinned memory with a non-blocking
-    copy; every batch hands the kernels a slice of that device tensor, so a batch is two launches and no copy."""
+    copy; every batch hands the kernels a slice of that device tensor, so a batch is two launches and no copy.
+    ``graphs`` (see ``PackedDataset.batch``): every batch also carries its ``SortedGraph`` under ``"graph"``, two more launches; the
+    dataset's frames are sorted once, when the first batch is drawn."""
 
     def __init__(self, packed: PackedDataset, batch_size=1, shuffle=False, drop_last=False,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, graphs=None):
+        _check_graphs(graphs)
         self.packed, self.batch_size, self.shuffle, self.drop_last = packed, int(batch_size), shuffle, drop_last
-        self.generator = generator
+        self.generator, self.graphs = generator, graphs
 
     def __len__(self) -> int:
         n = len(self.packed)
@@ -509,4 +635,4 @@ class PackedLoader:
         ids_dev, order_host = self.packed._upload(order), order.numpy()
         for i in range(len(self)):
             a, b = i * self.batch_size, min((i + 1) * self.batch_size, n)
-            yield self.packed._assemble(ids_dev[a:b], order_host[a:b])
+            yield self.packed._assemble(ids_dev[a:b], order_host[a:b], self.graphs)

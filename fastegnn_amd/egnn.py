@@ -266,6 +266,8 @@ class EGNN(nn.Module):
         if self._wide:
             from . import wide
             from .model import _DEBUG_CHECKS, _check_indices
+            if isinstance(edge_index, SortedGraph):
+                raise TypeError("fastegnn_amd: the wide path (hidden_nf > 64) takes edge_index as the reference does, an int64 [2, E] tensor")
             if _DEBUG_CHECKS:   # FASTEGNN_DEBUG_CHECKS=1: an out-of-range row / col would be an out-of-bounds gather or atomic
                 _check_indices(edge_index, torch.zeros(x.size(0), dtype=torch.long, device=x.device), x.size(0), 1)
             if edge_fea is not None and edge_fea.size(1) == 0:
@@ -275,8 +277,13 @@ class EGNN(nn.Module):
         if self._spec is None:
             self._build_spec()
         N = x.size(0)
-        key = (edge_index.data_ptr(), edge_index.size(1), edge_index._version, N)
-        graph = self._graph_cache.get(key) if self.cache_graphs else None
+        if isinstance(edge_index, SortedGraph):   # as FastEGNN takes one: used as it is, never cached
+            graph = edge_index
+            if graph.cscptr is None and self._spec.flags & K.F_DETERMINISTIC:
+                raise ValueError("fastegnn_amd: deterministic=True needs a SortedGraph built with csc=True")
+        else:
+            key = (edge_index.data_ptr(), edge_index.size(1), edge_index._version, N)
+            graph = self._graph_cache.get(key) if self.cache_graphs else None
         if graph is None:
             graph = SortedGraph(edge_index, N, csc=bool(self._spec.flags & K.F_DETERMINISTIC))
             if self.cache_graphs:

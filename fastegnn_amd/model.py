@@ -271,6 +271,37 @@ class SortedGraph:
         self.n_chunks = nch.value
         self._key = (edge_index.data_ptr(), E, edge_index._version, n_rows, n_src, row_begin)
 
+    @classmethod
+    def from_arrays(cls, rowptr, erow, col, perm, cscptr, csc_eid, chunk_row, n_chunks: int, n_rows: int, n_src: int,
+                    E: int) -> "SortedGraph":
+        """A graph over arrays the caller has already filled with what ``fastegnn_build_csr`` writes (data.PackedDataset assembles
+        them from per-frame indices): nothing is sorted and nothing launched here.  int32, contiguous, on one device: ``rowptr``
+        [n_rows + 1], ``erow`` / ``col`` / ``perm`` (and ``csc_eid``) at least E long, ``cscptr`` [n_src + 1] with ``csc_eid`` or both
+        None, ``chunk_row`` at least n_chunks + 1 long.  The graph carries no cache key (``_key`` is None) and is never entered into a
+        model's graph cache: the models take a ``SortedGraph`` as it is."""
+        n_chunks, n_rows, n_src, E = int(n_chunks), int(n_rows), int(n_src), int(E)
+        if n_rows < 0 or n_src < 0 or E < 0 or n_chunks < 1:
+            raise ValueError(f"SortedGraph.from_arrays: n_rows = {n_rows}, n_src = {n_src}, E = {E}, n_chunks = {n_chunks}")
+        if (cscptr is None) != (csc_eid is None):
+            raise ValueError("SortedGraph.from_arrays: cscptr and csc_eid are given or omitted together")
+        want = dict(rowptr=(rowptr, n_rows + 1, True), erow=(erow, E, False), col=(col, E, False), perm=(perm, E, False),
+                    chunk_row=(chunk_row, n_chunks + 1, False))
+        if cscptr is not None:
+            want.update(cscptr=(cscptr, n_src + 1, True), csc_eid=(csc_eid, E, False))
+        for name, (t, n, exact) in want.items():
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise TypeError(f"SortedGraph.from_arrays: {name} must be an int32 tensor, got {getattr(t, 'dtype', type(t))}")
+            if t.device != rowptr.device:
+                raise ValueError(f"SortedGraph.from_arrays: {name} lives on {t.device}, rowptr on {rowptr.device}")
+            if t.dim() != 1 or not t.is_contiguous() or (t.numel() != n if exact else t.numel() < n):
+                raise ValueError(f"SortedGraph.from_arrays: {name} has shape {list(t.shape)}, expected a contiguous "
+                                 f"[{n}{'' if exact else ' or more'}]")
+        g = cls.__new__(cls)
+        g.n_rows, g.n_src, g.E, g.n_chunks = n_rows, n_src, E, n_chunks
+        g.rowptr, g.erow, g.col, g.perm, g.cscptr, g.csc_eid, g.chunk_row = rowptr, erow, col, perm, cscptr, csc_eid, chunk_row
+        g._key = None
+        return g
+
     def struct(self) -> K.GraphT:
         g = K.GraphT()
         g.n_rows, g.n_src, g.n_edges, g.n_chunks = self.n_rows, self.n_src, self.E, self.n_chunks

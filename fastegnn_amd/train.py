@@ -365,12 +365,19 @@ class FusedAdam:
                                          d["scratch"].numel() * 4, st), "fastegnn_adam_step_dev")
 
 
+def _graph_or_edges(data):
+    """what the model gets as ``edge_index``: the batch's ready ``SortedGraph`` (``data['graph']``, data.PackedLoader(graphs=...)) when
+    there is one -- the model then sorts nothing -- else the int64 edge list"""
+    graph = data.get("graph")
+    return graph if graph is not None else data["edge_index"]
+
+
 def _forward_backward(model, optimizer, data: dict, sample_nodes, sigma, weight, sample_count=None):
     """augment + forward + MSE/MMD + backward of one iteration (everything of train_step in front of the optimizer)"""
     edge_attr = augment_edge_attr(data.get("edge_attr"), data["loc_0"], data["edge_index"])
     optimizer.zero_grad()
     loc_pred, vloc = model(node_loc=data["loc_0"], node_vel=data["vel_0"], node_attr=None,
-                           node_feat=data["node_feat"], edge_index=data["edge_index"], loc_mean=data["loc_mean"],
+                           node_feat=data["node_feat"], edge_index=_graph_or_edges(data), loc_mean=data["loc_mean"],
                            data_batch=data["batch"], edge_attr=edge_attr)
     loss, mse = mse_mmd_loss(loc_pred, vloc, data["loc_t"], sample_nodes, sigma, weight, sample_count)
     loss.backward()
@@ -411,12 +418,12 @@ def _evaluate_pass(model, loader, sigma, weight, sampler, num_sample):
             acc = torch.zeros(3, dtype=torch.float64, device=loc_0.device)
         edge_attr = augment_edge_attr(data.get("edge_attr"), loc_0, data["edge_index"])
         if egnn:   # utils/train.py:66-68: no virtual nodes, no MMD term
-            out = model(x=loc_0, h=data["node_feat"], edge_index=data["edge_index"], edge_fea=edge_attr, v=data["vel_0"])
+            out = model(x=loc_0, h=data["node_feat"], edge_index=_graph_or_edges(data), edge_fea=edge_attr, v=data["vel_0"])
             n_graphs = data["ptr"].numel() - 1 if "ptr" in data else data["loc_mean"].size(0)
             mse_mmd_eval(out[0], n_graphs, data["loc_t"], acc, sigma, weight)
             continue
         loc_pred, vloc = model(node_loc=loc_0, node_vel=data["vel_0"], node_attr=None, node_feat=data["node_feat"],
-                               edge_index=data["edge_index"], loc_mean=data["loc_mean"], data_batch=data["batch"], edge_attr=edge_attr)
+                               edge_index=_graph_or_edges(data), loc_mean=data["loc_mean"], data_batch=data["batch"], edge_attr=edge_attr)
         nodes = count = None
         if sampler is not None:
             nodes, count = sampler.draw(data["ptr"], min(int(num_sample), loc_0.size(0)))

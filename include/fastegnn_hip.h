@@ -601,6 +601,36 @@ int fastegnn_collate_gather(const int64_t *ids, int32_t B, const int64_t *src_no
                             int32_t n_frames, int64_t src_nodes, int64_t src_edges, const int64_t *node_ptr_out,
                             const int64_t *edge_ptr_out, int64_t n_nodes_out, int64_t n_edges_out, const void *const *src_tables,
                             void *const *dst_tables, const int32_t *widths, int64_t *batch_out, void *stream);
+/* The batch's SORTED graph without a sort.  ADDITIVE export, found by symbol: FASTEGNN_ABI_VERSION stays 108.
+ * fastegnn_build_csr is a stable sort by row and the frames of a batch own disjoint, ascending node ranges, so the index of the
+ * batch is the frames' own indices laid end to end with an offset added.  The packed dataset keeps those, built ONCE with
+ * fastegnn_build_csr (16 bytes per edge + 16 per node of device memory):
+ *   g_rowptr, g_cscptr  int64 [src_nodes + 1]  position of the node's first edge in the packed row-sorted (col-keyed) edge table;
+ *                       frames are contiguous: g_rowptr[src_node_ptr[f]] == src_edge_ptr[f], g_rowptr[src_nodes] == src_edges
+ *   g_erow, g_col       int32 [src_edges]      row / column of every row-sorted edge, node ids LOCAL to the frame
+ *   g_perm              int32 [src_edges]      position of the edge in the frame's own COO list
+ *   g_csc_eid           int32 [src_edges]      position inside the frame's row-sorted list, in col-keyed order
+ * ids .. n_edges_out are fastegnn_collate_gather's, node_ptr_out / edge_ptr_out fastegnn_collate_plan's.  Two launches whatever B is:
+ *   1. a segmented gather over the outputs (int32, the arrays of fastegnn_graph_t with n_rows = n_src = n_nodes_out): for frame
+ *      j = ids[i], no = node_ptr_out[i], eo = edge_ptr_out[i]
+ *        rowptr[no + k] = g_rowptr[src_node_ptr[j] + k] - src_edge_ptr[j] + eo,  rowptr[n_nodes_out] = n_edges_out  (cscptr likewise)
+ *        erow = g_erow + no,  col = g_col + no,  perm = g_perm + eo,  csc_eid = g_csc_eid + eo
+ *   2. the chunk launch of fastegnn_build_csr on the assembled rowptr: chunk_row [fastegnn_chunk_rows(n_edges_out)];
+ *      *n_chunks (HOST int) = n_edges_out / fastegnn_chunk_edges() + 1.
+ * The result equals fastegnn_build_csr(edge_index of the batch, n_edges_out, 0, n_nodes_out, n_nodes_out, ...) element for element.
+ * cscptr and csc_eid both NULL: no col-keyed index (g_cscptr / g_csc_eid may then be NULL too).  n_edges_out == 0: rowptr / cscptr
+ * all zero and the one-chunk chunk_row, as build_csr writes them; the edge arrays are not touched.  No atomics, no workspace, no
+ * read-back, no synchronisation.  The safety contract of _gather holds: ids clamped to [0, n_frames), an element outside its frame's
+ * source segment skipped, nothing read outside the packed tables or written beyond the totals given, whatever the device arrays
+ * hold.  FASTEGNN_E_INVALID before any launch for: B < 0, n_frames < 1, a negative size, n_nodes_out + 1 or n_edges_out beyond
+ * int32 (build_csr's argument types), nodes or edges with B == 0, a null pointer that would be used, cscptr without csc_eid or the
+ * reverse (g_cscptr / g_csc_eid alike), a col-keyed index asked for with edges but no g_cscptr. */
+int fastegnn_collate_graph(const int64_t *ids, int32_t B, const int64_t *src_node_ptr, const int64_t *src_edge_ptr, int32_t n_frames,
+                           int64_t src_nodes, int64_t src_edges, const int64_t *node_ptr_out, const int64_t *edge_ptr_out,
+                           int64_t n_nodes_out, int64_t n_edges_out, const int64_t *g_rowptr, const int32_t *g_erow,
+                           const int32_t *g_col, const int32_t *g_perm, const int64_t *g_cscptr, const int32_t *g_csc_eid,
+                           int32_t *rowptr, int32_t *erow, int32_t *col, int32_t *perm, int32_t *cscptr, int32_t *csc_eid,
+                           int32_t *chunk_row, int32_t *n_chunks, void *stream);
 
 /* ---- exchange steps of the sharded path (the reference has no distributed code) ----
  * RCCL collectives behind the C ABI: every call is enqueued on `stream` (ordered with the stage kernels, capturable

@@ -4,8 +4,11 @@ wall clock around an epoch that ends in one device synchronise; both loaders war
 median of EPOCHS epochs with min, max and inter-quartile range (the box's epoch-to-epoch spread).  Each shape twice: the loader
 alone (every batch is dropped as soon as it is built), and the loader with train_step on every batch.  Three shapes from seeds:
 cfg1-like and cfg2-like N-body frames at batch size 100, Water-3D-like clouds (r = 0.035 graphs of graphs.radius_graph_batch)
-at batch size 20.  The batches of the two loaders are compared with torch.equal first.  Prints what profiles/packed_loader.txt
-holds.
+at batch size 20.  The batches of the two loaders are compared with torch.equal first.  A third loader,
+PackedLoader(graphs=model.deterministic_for), hands every batch over with its sorted graph assembled from indices sorted once
+(PackedDataset.build_graphs), so that train_step sorts nothing: its graphs are compared with the model's own first, and it
+alternates with the other two.  Prints what profiles/packed_loader_graphs.txt holds (profiles/packed_loader.txt: the same without
+the third loader).
 
     python tools/gpu_loader_timing.py [output file]
 """
@@ -116,7 +119,7 @@ def line(name, ts, n_batches):
 
 def main():
     out = [f"device: {torch.cuda.get_device_name(0)}; host wall clock around one epoch ending in one device synchronise; "
-           f"the two loaders alternate in one process"]
+           f"the loaders alternate in one process"]
     shapes = [("cfg1-like: 2000 frames x 5 nodes x 20 edges, batch size 100", lambda: nbody_frames(2000, 5, 1), 100),
               ("cfg2-like: 500 frames x 100 nodes x 9900 edges, batch size 100", lambda: nbody_frames(500, 100, 2), 100),
               ("Water-3D-like: 60 frames x 7600..8400 nodes, r = 0.035 in a 0.42^3 box, batch size 20", lambda: water_frames(60, 3), 20)]
@@ -150,19 +153,38 @@ def main():
         out.append(f"  the gather launch alone (HIP events around the launch, the library's profiler): {us:.1f} us mean of {n} = "
                    f"{bytes_moved / us / 1e3:.0f} GB/s read + written;  a torch copy_ of the same bytes: "
                    f"{bytes_moved / copy_us(bytes_moved // 2) / 1e3:.0f} GB/s")
-        loaders = [("DataLoader", old), ("PackedLoader", new)]
+        model = fastegnn_amd.FastEGNN(node_feat_nf=2, node_attr_nf=0, edge_attr_nf=2, hidden_nf=64, virtual_channels=C,
+                                      device="cuda", n_layers=4)
+        # the third loader: every batch with the sorted graph the model would build (the same edge-backward form: deterministic_for)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        packed.build_graphs()
+        torch.cuda.synchronize()
+        t_pack = time.perf_counter() - t0
+        g_bytes = sum(t.numel() * t.element_size() for t in packed.graph_tables.values())
+        gl = D.PackedLoader(packed, batch_size=bs, shuffle=True, generator=torch.Generator().manual_seed(9), graphs=model.deterministic_for)
+        arrays = ("rowptr", "erow", "col", "perm", "cscptr", "csc_eid")
+        same_g = True
+        for b in gl:
+            want, got = model.sorted_graph(b["edge_index"], b.num_nodes), b["graph"]
+            same_g &= got.n_chunks == want.n_chunks and (got.cscptr is None) == (want.cscptr is None)
+            same_g &= all(torch.equal(getattr(got, k), getattr(want, k)) for k in arrays if getattr(want, k) is not None)
+            same_g &= torch.equal(got.chunk_row[:got.n_chunks + 1], want.chunk_row[:want.n_chunks + 1])
+        model._graph_cache.clear()
+        out.append(f"  build_graphs (once per dataset): {t_pack * 1e3:.1f} ms, {g_bytes / 1e6:.2f} MB of per-frame sorted indices; "
+                   f"col-keyed index in the first batch: {model.deterministic_for(first['edge_index'].size(1))}; assembled graphs "
+                   f"equal the model's own (torch.equal, every array, every batch): {same_g}")
+        loaders = [("DataLoader", old), ("PackedLoader", new), ("Packed+graph", gl)]
         out.append("  loader alone:")
         ts = epoch_times(loaders, lambda batch: None)
         out += [line(k, ts[k], nb) for k, _ in loaders]
-        model = fastegnn_amd.FastEGNN(node_feat_nf=2, node_attr_nf=0, edge_attr_nf=2, hidden_nf=64, virtual_channels=C,
-                                      device="cuda", n_layers=4)
         opt = FusedAdam(model.parameters(), lr=5e-4, weight_decay=1e-12)
         smp = MMDSampler(0)
         out.append("  loader + train_step (FastEGNN hidden 64, 4 layers, C = 3, device-side MMD sample):")
         ts = epoch_times(loaders, lambda batch: train_step(model, opt, batch, None, sigma=1.0, weight=0.01, sampler=smp,
                                                            num_sample=3 * C))
         out += [line(k, ts[k], nb) for k, _ in loaders]
-        del frames, packed, old, new, model, opt
+        del frames, packed, old, new, gl, model, opt
         torch.cuda.empty_cache()
     text = "\n".join(out)
     print(text)
