@@ -6,6 +6,6 @@ Only the hot path of GLAD-RUC/FastEGNN lives here: the drop-in ``FastEGNN`` modu
 from .model import FastEGNN, SortedGraph  # noqa: F401
 from .egnn import EGNN  # noqa: F401
 from .fastrf import FastRF  # noqa: F401
-from .train import FusedAdam, MMDSampler, evaluate, train_step  # noqa: F401
+from .train import FusedAdam, MMDSampler, evaluate, train_epoch, train_step  # noqa: F401
 
-__all__ = ["FastEGNN", "FastRF", "EGNN", "SortedGraph", "FusedAdam", "MMDSampler", "train_step", "evaluate"]
+__all__ = ["FastEGNN", "FastRF", "EGNN", "SortedGraph", "FusedAdam", "MMDSampler", "train_step", "train_epoch", "evaluate"]

@@ -201,6 +201,12 @@ def lib(act: bool = False, wide=None):
     # the batch's sorted graph from the packed dataset's per-frame indices: additive
     L.fastegnn_collate_graph.argtypes = ([_vp, _i32, _vp, _vp, _i32, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, C.c_int64] + [_vp] * 6
                                          + [_vp] * 7 + [C.POINTER(_i32), _vp])
+    # equal-sized frames: the order drawn on the device, the batch and its graph in one launch over static buffers: additive
+    L.fastegnn_collate_draw.argtypes = [_vp, _i32, _i32, _i32, _i32, _vp, _vp]
+    L.fastegnn_collate_gather_uniform.argtypes = ([_vp, _i32, _i32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(_vp),
+                                                   C.POINTER(_vp), C.POINTER(_i32)] + [_vp] * 6 + [_vp] * 7 + [C.POINTER(_i32), _vp])
+    # a training step's (loss, mse) into the epoch's three fp64 words: additive
+    L.fastegnn_loss_accumulate.argtypes = [_vp, _vp, _i32, _vp, _vp]
     L.fastegnn_selftest_gemm.argtypes = [_vp, _vp, _vp, _i32, _vp]
     L.fastegnn_selftest_rm.argtypes = [_vp, _vp, _vp, _i32, _i32, _vp]
     L.fastegnn_selftest_jreduce.argtypes = [_vp, _vp, _vp]
@@ -295,7 +301,7 @@ EXPORTED = STAGE_FUNCS + [
     "fastegnn_cutoff_tmp_bytes", "fastegnn_cutoff_edges", "fastegnn_nbody_cutoff_edges",
     "fastegnn_radius_graph_batch_ws_bytes", "fastegnn_radius_graph_batch_count", "fastegnn_radius_graph_batch_fill",
     "fastegnn_cutoff_batch_tmp_bytes", "fastegnn_cutoff_edges_batch", "fastegnn_collate_plan", "fastegnn_collate_gather",
-    "fastegnn_collate_graph",
+    "fastegnn_collate_graph", "fastegnn_collate_draw", "fastegnn_collate_gather_uniform", "fastegnn_loss_accumulate",
     "fastegnn_profile_enable", "fastegnn_profile_kernels", "fastegnn_profile_name", "fastegnn_profile_collect",
     "fastegnn_comm_unique_id_bytes", "fastegnn_comm_unique_id", "fastegnn_comm_init", "fastegnn_comm_destroy", "fastegnn_comm_rank",
     "fastegnn_comm_world", "fastegnn_comm_all_reduce", "fastegnn_comm_all_gather", "fastegnn_comm_reduce_scatter",

@@ -11,7 +11,12 @@
 //   graph   (optional, two more launches) the batch's SORTED index -- what fastegnn_build_csr would make of the batch's edge_index --
 //           from the frames' own sorted indices, kept in the packed dataset: the same segmented walk with an offset added to every
 //           integer, then csr.hip's chunk kernel on the assembled rowptr.  No sort, no atomics, no workspace.
+// Equal-sized frames (data.py: PackedStream) need neither offsets nor a search, and their order is drawn here:
+//   draw            one workgroup: the next batch's frame numbers from {seed, epoch, cursor} in device memory (keyed_perm.h)
+//   gather_uniform  one launch over every output table AND the graph arrays: slot = element / segment length, 16- or 8-byte
+//                   accesses wherever a frame's segment and the two base addresses allow them; then the chunk kernel.
 #include "kernels.h"
+#include "keyed_perm.h"
 
 namespace fe {
 
@@ -327,6 +332,211 @@ static void add_job(ClJobs &J, const void *src, void *dst, long long n, long lon
   J.n_tiles += (n + CL_TILE - 1) / CL_TILE;
 }
 
+// ---- equal-sized frames (fastegnn_collate_draw / fastegnn_collate_gather_uniform): the order drawn here, a frame's place a product ----
+constexpr uint64_t CU_STREAM_TAG = 0x5354524Dull;   // the `b` of the keyed permutation: apart from every graph number of an MMD draw
+
+// One workgroup.  Every thread reads the three words first; thread 0 writes cursor and epoch behind the barrier that follows the last
+// id, so all ids of a draw come from one state.
+__global__ __launch_bounds__(CL_PLAN_THREADS) void collate_draw_kernel(uint64_t *state, int B, int n_frames, int shuffle, int advance,
+                                                                        int64_t *__restrict__ ids_out) {
+  const uint64_t seed = state[0], epoch = state[1], cursor = state[2];
+  const uint64_t nb = (uint64_t)(n_frames / B);   // >= 1: the host checked n_frames >= B >= 1
+  const uint64_t c = cursor % nb;
+  const uint64_t gkey = perm_draw_key(seed, epoch);
+  for (int base = 0; base < B; base += CL_PLAN_THREADS) {
+    const int i = base + (int)threadIdx.x;
+    if (i < B) {
+      const uint64_t j = c * (uint64_t)B + (uint64_t)i;   // < nb * B <= n_frames
+      ids_out[i] = (int64_t)(shuffle ? keyed_perm(gkey, CU_STREAM_TAG, (uint64_t)n_frames, j) : j);
+    }
+  }
+  __syncthreads();
+  if (advance && threadIdx.x == 0) {
+    if (c + 1 >= nb) {
+      state[2] = 0;
+      state[1] = epoch + 1;
+    } else {
+      state[2] = c + 1;
+    }
+  }
+}
+
+constexpr int CU_MAX_JOBS = FASTEGNN_COLLATE_TABLES + 1 + 6;   // the float tables, the two rows of edge_index, the six graph arrays
+// CU_ADD32 / CU_ADD64: units of 4, 8 or 16 bytes holding 32- / 64-bit integers, every one + slot * add_mul (a float table is CU_ADD32
+// with add_mul = 0: adding 0 to the bit pattern is the copy).  CU_PTR: rowptr / cscptr, int64 -> int32, one element per lane.
+enum { CU_ADD32 = 0, CU_ADD64 = 1, CU_PTR = 2, CU_ZERO = 3 };
+
+struct CuJob {
+  const void *src;
+  void *dst;
+  long long n;         // output units
+  long long tile0;     // first tile of the job
+  long long seg;       // units per frame, > 0
+  long long add_mul;   // batch slot f adds f * add_mul to every integer
+  long long sub_mul;   // CU_PTR: frame id takes id * sub_mul off (its first edge in the packed table)
+  int op, unit;        // unit: bytes per lane access
+};
+struct CuJobs {
+  CuJob job[CU_MAX_JOBS];
+  const int64_t *ids;
+  long long n_tiles, n_edges_out;
+  int n_jobs, n_frames;
+};
+
+template <int UNIT> struct CuVec;
+template <> struct CuVec<4> { using type = unsigned; };
+template <> struct CuVec<8> { using type = uint2; };
+template <> struct CuVec<16> { using type = uint4; };
+
+__device__ __forceinline__ void cu_add64(unsigned &lo, unsigned &hi, long long a) {
+  const unsigned long long v = (((unsigned long long)hi << 32) | lo) + (unsigned long long)a;
+  lo = (unsigned)v;
+  hi = (unsigned)(v >> 32);
+}
+template <bool I64> __device__ __forceinline__ void cu_add(unsigned &v, long long a) { v += (unsigned)a; }
+template <bool I64> __device__ __forceinline__ void cu_add(uint2 &v, long long a) {
+  if (I64) cu_add64(v.x, v.y, a);
+  else { v.x += (unsigned)a; v.y += (unsigned)a; }
+}
+template <bool I64> __device__ __forceinline__ void cu_add(uint4 &v, long long a) {
+  if (I64) { cu_add64(v.x, v.y, a); cu_add64(v.z, v.w, a); }
+  else { v.x += (unsigned)a; v.y += (unsigned)a; v.z += (unsigned)a; v.w += (unsigned)a; }
+}
+
+// slot and offset inside the slot of unit e, from the tile's first slot f0 (one 64-bit division per tile; a unit's own is 32-bit
+// whenever the frame's segment allows it)
+__device__ __forceinline__ void cu_locate(long long e, long long f0, long long seg, long long &f, long long &local) {
+  const long long d = e - f0 * seg;   // < seg + CL_TILE
+  const long long q = seg < (1ll << 31) - CL_TILE ? (long long)((unsigned)d / (unsigned)seg) : d / seg;
+  f = f0 + q;
+  local = d - q * seg;
+}
+
+// One tile of one job: CL_UNROLL loads in flight before the stores, consecutive lanes on consecutive units.
+template <int UNIT, bool I64>
+__device__ __forceinline__ void uniform_tile(const CuJob &jb, const int64_t *__restrict__ ids, int n_frames, long long e0,
+                                             long long e1) {
+  using V = typename CuVec<UNIT>::type;
+  const V *__restrict__ src = (const V *)jb.src;
+  V *__restrict__ dst = (V *)jb.dst;
+  const long long seg = jb.seg, f0 = e0 / seg;
+  long long src_at[CL_UNROLL], add[CL_UNROLL];
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) {
+    const long long e = e0 + u * CL_THREADS + threadIdx.x;
+    src_at[u] = -1;
+    add[u] = 0;
+    if (e < e1) {
+      long long f, local;
+      cu_locate(e, f0, seg, f, local);
+      src_at[u] = clamp_id(ids[f], n_frames) * seg + local;
+      add[u] = f * jb.add_mul;
+    }
+  }
+  V v[CL_UNROLL];
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u)
+    if (src_at[u] >= 0) v[u] = src[src_at[u]];
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u)
+    if (src_at[u] >= 0) {
+      cu_add<I64>(v[u], add[u]);
+      dst[e0 + u * CL_THREADS + threadIdx.x] = v[u];
+    }
+}
+
+// rowptr / cscptr: element e < n - 1 is node `local` of slot f; the last one is the batch's edge total
+__device__ __forceinline__ void uniform_ptr_tile(const CuJob &jb, const int64_t *__restrict__ ids, int n_frames, long long e0,
+                                                 long long e1, long long n_edges_out) {
+  const long long *__restrict__ src = (const long long *)jb.src;
+  int32_t *__restrict__ dst = (int32_t *)jb.dst;
+  const long long seg = jb.seg, f0 = e0 / seg;
+  long long src_at[CL_UNROLL], add[CL_UNROLL], v[CL_UNROLL];
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) {
+    const long long e = e0 + u * CL_THREADS + threadIdx.x;
+    src_at[u] = -1;
+    add[u] = 0;
+    if (e < e1 && e < jb.n - 1) {
+      long long f, local;
+      cu_locate(e, f0, seg, f, local);
+      const long long id = clamp_id(ids[f], n_frames);
+      src_at[u] = id * seg + local;
+      add[u] = f * jb.add_mul - id * jb.sub_mul;
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) v[u] = src_at[u] >= 0 ? src[src_at[u]] : 0;
+#pragma unroll
+  for (int u = 0; u < CL_UNROLL; ++u) {
+    const long long e = e0 + u * CL_THREADS + threadIdx.x;
+    if (src_at[u] >= 0) dst[e] = (int32_t)(v[u] + add[u]);
+    else if (e == jb.n - 1 && e < e1) dst[e] = (int32_t)n_edges_out;
+  }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void collate_gather_uniform_kernel(const CuJobs J) {
+  for (long long tile = blockIdx.x; tile < J.n_tiles; tile += gridDim.x) {
+    int j = 0;
+    for (int k = 1; k < J.n_jobs; ++k)
+      if (tile >= J.job[k].tile0) j = k;
+    const CuJob &jb = J.job[j];
+    const long long e0 = (tile - jb.tile0) * CL_TILE;
+    const long long e1 = e0 + CL_TILE < jb.n ? e0 + CL_TILE : jb.n;
+    if (jb.op == CU_ZERO) {
+      int32_t *__restrict__ dst = (int32_t *)jb.dst;
+      for (long long e = e0 + threadIdx.x; e < e1; e += CL_THREADS) dst[e] = 0;
+    } else if (jb.op == CU_PTR) {
+      uniform_ptr_tile(jb, J.ids, J.n_frames, e0, e1, J.n_edges_out);
+    } else if (jb.op == CU_ADD64) {
+      if (jb.unit == 16) uniform_tile<16, true>(jb, J.ids, J.n_frames, e0, e1);
+      else uniform_tile<8, true>(jb, J.ids, J.n_frames, e0, e1);
+    } else {
+      if (jb.unit == 16) uniform_tile<16, false>(jb, J.ids, J.n_frames, e0, e1);
+      else if (jb.unit == 8) uniform_tile<8, false>(jb, J.ids, J.n_frames, e0, e1);
+      else uniform_tile<4, false>(jb, J.ids, J.n_frames, e0, e1);
+    }
+  }
+}
+
+// the widest of 16, 8 and `elem` bytes that divides the frame's segment and both base addresses
+static int cu_unit(const void *src, const void *dst, long long seg_bytes, int elem) {
+  const unsigned long long any = (unsigned long long)(uintptr_t)src | (unsigned long long)(uintptr_t)dst | (unsigned long long)seg_bytes;
+  return any % 16 == 0 ? 16 : (any % 8 == 0 ? 8 : elem);
+}
+
+// a job of `elems_per_frame` integers of `elem` bytes per frame over B frames; nothing for an empty table
+static void add_uniform_job(CuJobs &J, const void *src, void *dst, long long elems_per_frame, int B, int elem, int op,
+                            long long add_mul) {
+  if (elems_per_frame <= 0) return;
+  CuJob &jb = J.job[J.n_jobs++];
+  jb.unit = cu_unit(src, dst, elems_per_frame * elem, elem);
+  jb.src = src;
+  jb.dst = dst;
+  jb.seg = elems_per_frame * elem / jb.unit;
+  jb.n = jb.seg * B;
+  jb.tile0 = J.n_tiles;
+  jb.add_mul = add_mul;
+  jb.sub_mul = 0;
+  jb.op = op;
+  J.n_tiles += (jb.n + CL_TILE - 1) / CL_TILE;
+}
+
+static void add_uniform_ptr_job(CuJobs &J, const int64_t *src, int32_t *dst, long long nodes_per_frame, long long edges_per_frame,
+                                int B) {
+  CuJob &jb = J.job[J.n_jobs++];
+  jb.src = src;
+  jb.dst = dst;
+  jb.unit = 4;
+  jb.seg = nodes_per_frame > 0 ? nodes_per_frame : 1;   // a dataset of empty frames: the job is its last element alone
+  jb.n = nodes_per_frame * B + 1;
+  jb.tile0 = J.n_tiles;
+  jb.add_mul = edges_per_frame;
+  jb.sub_mul = edges_per_frame;
+  jb.op = edges_per_frame > 0 && nodes_per_frame > 0 ? CU_PTR : CU_ZERO;
+  J.n_tiles += (jb.n + CL_TILE - 1) / CL_TILE;
+}
+
 }  // namespace fe
 
 using namespace fe;
@@ -430,6 +640,83 @@ int fastegnn_collate_graph(const int64_t *ids, int32_t B, const int64_t *src_nod
   *n_chunks = nch;
   launch_chunk_rows(rowptr, (int)n_nodes_out, nch, chunk_row, st);
   return check_launch("collate_graph");
+}
+
+int fastegnn_collate_draw(uint64_t *state, int32_t B, int32_t n_frames, int32_t shuffle, int32_t advance, int64_t *ids_out,
+                          void *stream) {
+  FE_REQUIRE(state && ids_out, "collate_draw: null pointer");
+  FE_REQUIRE(B >= 1, "collate_draw: B < 1");
+  FE_REQUIRE(n_frames >= B, "collate_draw: n_frames < B (a stream yields full batches only)");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope _ps(K_MISC, st);
+  hipLaunchKernelGGL(collate_draw_kernel, dim3(1), dim3(CL_PLAN_THREADS), 0, st, state, B, n_frames, shuffle, advance, ids_out);
+  return check_launch("collate_draw");
+}
+
+int fastegnn_collate_gather_uniform(const int64_t *ids, int32_t B, int32_t n_frames, int64_t nodes_per_frame,
+                                    int64_t edges_per_frame, int64_t src_nodes, int64_t src_edges, const void *const *src_tables,
+                                    void *const *dst_tables, const int32_t *widths, const int64_t *g_rowptr, const int32_t *g_erow,
+                                    const int32_t *g_col, const int32_t *g_perm, const int64_t *g_cscptr, const int32_t *g_csc_eid,
+                                    int32_t *rowptr, int32_t *erow, int32_t *col, int32_t *perm, int32_t *cscptr, int32_t *csc_eid,
+                                    int32_t *chunk_row, int32_t *n_chunks, void *stream) {
+  FE_REQUIRE(B >= 1, "collate_gather_uniform: B < 1");
+  FE_REQUIRE(n_frames >= 1, "collate_gather_uniform: the packed dataset holds no frame");
+  FE_REQUIRE(nodes_per_frame >= 0 && edges_per_frame >= 0, "collate_gather_uniform: negative size");
+  FE_REQUIRE(nodes_per_frame <= (1ll << 40) && edges_per_frame <= (1ll << 40), "collate_gather_uniform: frame size out of range");
+  FE_REQUIRE(edges_per_frame == 0 || nodes_per_frame >= 1, "collate_gather_uniform: edges in frames without nodes");
+  FE_REQUIRE(src_nodes == (long long)n_frames * nodes_per_frame && src_edges == (long long)n_frames * edges_per_frame,
+             "collate_gather_uniform: src_nodes / src_edges are not n_frames times the per-frame counts");
+  FE_REQUIRE(ids && src_tables && dst_tables && widths, "collate_gather_uniform: null pointer");
+  const long long n_nodes_out = (long long)B * nodes_per_frame, n_edges_out = (long long)B * edges_per_frame;
+  CuJobs J = {};
+  for (int t = 0; t < FASTEGNN_COLLATE_TABLES - 1; ++t) {
+    FE_REQUIRE(widths[t] >= 0 && widths[t] <= (1 << 20), "collate_gather_uniform: row width out of range (0 .. 2^20)");
+    const long long count = t < FASTEGNN_COLLATE_EDGE_ATTR ? nodes_per_frame : (t == FASTEGNN_COLLATE_EDGE_ATTR ? edges_per_frame : 1);
+    FE_REQUIRE(count * widths[t] == 0 || (src_tables[t] && dst_tables[t]), "collate_gather_uniform: null table");
+    add_uniform_job(J, src_tables[t], dst_tables[t], count * widths[t], B, 4, CU_ADD32, 0);
+  }
+  const int64_t *ei_src = (const int64_t *)src_tables[FASTEGNN_COLLATE_EDGE_INDEX];
+  int64_t *ei_dst = (int64_t *)dst_tables[FASTEGNN_COLLATE_EDGE_INDEX];
+  FE_REQUIRE(edges_per_frame == 0 || (ei_src && ei_dst), "collate_gather_uniform: null edge_index");
+  for (int r = 0; r < 2 && edges_per_frame > 0; ++r)   // row r of [2,E] on both sides
+    add_uniform_job(J, ei_src + (size_t)r * src_edges, ei_dst + (size_t)r * n_edges_out, edges_per_frame, B, 8, CU_ADD64,
+                    nodes_per_frame);
+  const bool want_graph = rowptr != nullptr;
+  if (want_graph) {
+    FE_REQUIRE(chunk_row && n_chunks, "collate_gather_uniform: null output");
+    FE_REQUIRE(n_nodes_out < 0x7fffffffll && n_edges_out <= 0x7fffffffll,
+               "collate_gather_uniform: the batch exceeds the int32 sizes of build_csr");
+    FE_REQUIRE((cscptr == nullptr) == (csc_eid == nullptr), "collate_gather_uniform: cscptr and csc_eid are given or omitted together");
+    const bool want_csc = cscptr != nullptr;
+    // the packed tables are looked at only where there are edges: a dataset without any holds empty (null) edge arrays
+    FE_REQUIRE(edges_per_frame == 0 || (g_rowptr && g_erow && g_col && g_perm && erow && col && perm),
+               "collate_gather_uniform: null pointer");
+    FE_REQUIRE(edges_per_frame == 0 || !want_csc || (g_cscptr && g_csc_eid),
+               "collate_gather_uniform: a col-keyed index is asked for but the packed tables hold none");
+    add_uniform_ptr_job(J, g_rowptr, rowptr, nodes_per_frame, edges_per_frame, B);
+    if (want_csc) add_uniform_ptr_job(J, g_cscptr, cscptr, nodes_per_frame, edges_per_frame, B);
+    add_uniform_job(J, g_erow, erow, edges_per_frame, B, 4, CU_ADD32, nodes_per_frame);
+    add_uniform_job(J, g_col, col, edges_per_frame, B, 4, CU_ADD32, nodes_per_frame);
+    add_uniform_job(J, g_perm, perm, edges_per_frame, B, 4, CU_ADD32, edges_per_frame);
+    if (want_csc) add_uniform_job(J, g_csc_eid, csc_eid, edges_per_frame, B, 4, CU_ADD32, edges_per_frame);
+  }
+  if (J.n_tiles == 0) return FASTEGNN_OK;   // nothing to write: no launch on an empty grid
+  hipStream_t st = (hipStream_t)stream;
+  J.ids = ids;
+  J.n_frames = n_frames;
+  J.n_edges_out = n_edges_out;
+  const int grid = (int)(J.n_tiles < CL_MAX_BLOCKS ? J.n_tiles : CL_MAX_BLOCKS);
+  {
+    ProfScope _ps(K_MISC, st);
+    hipLaunchKernelGGL(collate_gather_uniform_kernel, dim3(grid), dim3(CL_THREADS), 0, st, J);
+  }
+  if (want_graph) {
+    ProfScope _ps(K_MISC, st);
+    const int nch = csr_chunk_count((int)n_edges_out);
+    *n_chunks = nch;
+    launch_chunk_rows(rowptr, (int)n_nodes_out, nch, chunk_row, st);
+  }
+  return check_launch("collate_gather_uniform");
 }
 
 }  // extern "C"

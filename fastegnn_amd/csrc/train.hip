@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "keyed_perm.h"
 
 namespace fe {
 
@@ -98,25 +99,14 @@ __global__ __launch_bounds__(256) void loss_mmd_kernel(const float *pred, const 
   }
 }
 
-// ---- the device-side MMD sample (fastegnn_mmd_sample; the permutation is defined in include/fastegnn_hip.h, integers only) ----
-__host__ __device__ inline uint64_t mix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ inline uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7FEB352Du;
-  x ^= x >> 15; x *= 0x846CA68Bu;
-  return x ^ (x >> 16);
-}
-constexpr int MMD_ROUNDS = 8;
+// ---- the device-side MMD sample (fastegnn_mmd_sample; the permutation is defined in include/fastegnn_hip.h and lives in
+// keyed_perm.h, which the packed stream's draw shares) ----
 // One thread per entry (b, j), grid-stride; thread i < B also writes sample_count[i].  Reads rng and ptr, writes its own outputs:
 // no atomics, and every workgroup sees the same counter because nothing in this launch writes it (mmd_advance_kernel does, behind).
 __global__ __launch_bounds__(256) void mmd_sample_kernel(const int64_t *ptr, int B, int S, const uint64_t *rng, int32_t *nodes,
                                                          int32_t *count) {
   const long total = (long)B * S, stride = (long)gridDim.x * 256;
-  const uint64_t gkey = mix64(mix64(rng[0]) ^ rng[1]);
+  const uint64_t gkey = perm_draw_key(rng[0], rng[1]);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total || i < B; i += stride) {
     if (i < B) {
       const int64_t n = ptr[i + 1] - ptr[i];
@@ -127,28 +117,22 @@ __global__ __launch_bounds__(256) void mmd_sample_kernel(const int64_t *ptr, int
     const int64_t p0 = ptr[b], n = ptr[b + 1] - p0;
     if (j >= n) { nodes[i] = -1; continue; }
     if (n <= S) { nodes[i] = (int32_t)(p0 + j); continue; }
-    int k = 64 - __builtin_clzll((unsigned long long)(n - 1));   // ceil(log2 n), n >= 2 here
-    if (k < 2) k = 2;
-    k += k & 1;
-    const int h = k >> 1;
-    const uint64_t mask = (1ull << h) - 1, g = mix64(gkey ^ (uint64_t)b);
-    uint64_t key[MMD_ROUNDS];
-    for (int r = 0; r < MMD_ROUNDS; ++r) key[r] = mix64(g + (uint64_t)r);
-    uint64_t x = (uint64_t)j;
-    // cycle walking: E is a bijection of [0, 2^k) and j < n, so the walk stays on j's own cycle, which holds at most 2^k - n values
-    // >= n -- it ends within 2^k - n + 1 applications (2^k / n < 4 on average)
-    do {
-      for (int r = 0; r < MMD_ROUNDS; ++r) {
-        const uint64_t L = x >> h, R = x & mask;
-        const uint64_t F = (uint64_t)(mix32((uint32_t)R ^ (uint32_t)key[r]) ^ (uint32_t)(key[r] >> 32)) & mask;
-        x = (R << h) | (L ^ F);
-      }
-    } while (x >= (uint64_t)n);
+    const uint64_t x = keyed_perm(gkey, (uint64_t)b, (uint64_t)n, (uint64_t)j);   // n > S >= 1 here
     nodes[i] = (int32_t)(p0 + (int64_t)x);
   }
 }
 __global__ void mmd_advance_kernel(uint64_t *rng) {
   if (blockIdx.x == 0 && threadIdx.x == 0) rng[1] += 1;
+}
+
+// fastegnn_loss_accumulate: a training step's (loss, mse) into the three fp64 words of an epoch (loss_eval_kernel's acc)
+__global__ void loss_accumulate_kernel(const float *loss, const float *mse, int B, double *acc) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const double b = (double)B;
+    acc[0] += b * (double)mse[0];
+    acc[1] += b * (double)loss[0];
+    acc[2] += b;
+  }
 }
 
 // torch.optim.Adam (no amsgrad; weight decay folded into the gradient), up to 24 tensors per launch.  Each tensor carries its
@@ -474,6 +458,14 @@ int fastegnn_loss_mse_mmd_eval(const float *loc_pred, const float *loc_t, const 
   hipLaunchKernelGGL(loss_eval_kernel, dim3(1), dim3(EVAL_THREADS), lds, (hipStream_t)stream, loc_pred, loc_t, vloc,
                      mmd ? sample_nodes : nullptr, sample_count, (long)N * 3, B, C, S, sigma, weight, acc);
   return check_launch("loss_eval_kernel");
+}
+
+int fastegnn_loss_accumulate(const float *loss, const float *mse, int32_t B, double *acc, void *stream) {
+  FE_REQUIRE(loss && mse && acc, "loss_accumulate: null pointer");
+  FE_REQUIRE(B >= 0, "loss_accumulate: B < 0");
+  if (B == 0) return FASTEGNN_OK;   // no graph: acc stays as it is
+  hipLaunchKernelGGL(loss_accumulate_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, loss, mse, B, acc);
+  return check_launch("loss_accumulate");
 }
 
 int fastegnn_mmd_sample(const int64_t *ptr, int32_t B, int32_t S, uint64_t *rng, int32_t advance, int32_t *sample_nodes,

@@ -17,6 +17,8 @@
   is two kernel launches (csrc/collate.hip) whatever its size, with no host-to-device copy and no synchronisation.  With
   ``graphs=...`` a batch also carries its ``SortedGraph``, assembled by two more launches from per-frame indices sorted once
   (``PackedDataset.build_graphs``): the model then sorts nothing per batch.
+* ``PackedStream`` -- a packed dataset of EQUAL-SIZED frames (the N-body sets) streamed through buffers allocated once: the order
+  is drawn on the device and ``next()`` is two or three launches with no host work at all, the same every time (capturable).
 
 All processing is vectorised over the systems of a file and runs on the device the caller names.
 """
@@ -364,7 +366,8 @@ _NO_CPU = "fastegnn_amd: PackedDataset.batch needs device-resident tables (there
 class HipCollateOps:
     """The two device calls of a packed batch on libfastegnn_hip.so (the product path).  tests/packed_ref.py restates them in
     torch so that tests/test_packed_cpu.py can drive the loader's orchestration without a GPU (the ``wide.HipOps`` precedent).
-    ``sort`` and ``graph`` are the two calls behind a batch's sorted graph (tests/packed_graph_ref.py restates them likewise)."""
+    ``sort`` and ``graph`` are the two calls behind a batch's sorted graph (tests/packed_graph_ref.py restates them likewise), ``draw``
+    and ``gather_uniform`` the two behind a ``PackedStream`` batch (tests/packed_stream_ref.py)."""
 
     @staticmethod
     def plan(ids, src_node_ptr, src_edge_ptr, node_ptr_out, edge_ptr_out) -> None:
@@ -422,6 +425,47 @@ class HipCollateOps:
                                                K.ptr(node_ptr_out), K.ptr(edge_ptr_out), n_nodes_out, n_edges_out,
                                                *[K.ptr(t) for t in src_graph], *[K.ptr(t) for t in dst_graph], K.ptr(chunk_row),
                                                C.byref(nch), _stream(ids.device)), "fastegnn_collate_graph")
+        return nch.value
+
+    @staticmethod
+    def draw(state, batch_size, n_frames, shuffle, advance, ids_out) -> None:
+        """ids_out int64 [B] <- the frame numbers of the next batch of a stream (fastegnn_collate_draw); ``state``: int64 [4] holding
+        the bit patterns of {seed, epoch, cursor, reserved}, advanced on the device when ``advance``.  One launch."""
+        if not ids_out.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        from . import _lib as K
+        from .model import _stream
+        K.check(K.lib().fastegnn_collate_draw(K.ptr(state), batch_size, n_frames, 1 if shuffle else 0, 1 if advance else 0,
+                                              K.ptr(ids_out), _stream(ids_out.device)), "fastegnn_collate_draw")
+
+    @staticmethod
+    def uniform_call(ids, n_frames, nodes_per_frame, edges_per_frame, src_tables, dst_tables, src_graph, dst_graph, chunk_row):
+        """the ctypes arguments of one ``gather_uniform`` call, built ONCE for buffers that stay where they are (``PackedStream``)"""
+        import ctypes as C
+        from . import _lib as K
+        n = len(_PACK_KEYS)
+        src = (C.c_void_p * n)(*[t.data_ptr() or None for t in src_tables])
+        dst = (C.c_void_p * n)(*[t.data_ptr() or None for t in dst_tables])
+        widths = (C.c_int32 * (n - 1))(*[math.prod(t.shape[1:]) for t in src_tables[:n - 1]])
+        nch = C.c_int32(0)
+        graph = [K.ptr(t) for t in src_graph] + [K.ptr(t) for t in dst_graph] + [K.ptr(chunk_row)] if dst_graph is not None \
+            else [None] * 13
+        return [K.ptr(ids), ids.numel(), n_frames, nodes_per_frame, edges_per_frame, n_frames * nodes_per_frame,
+                n_frames * edges_per_frame, src, dst, widths, *graph, C.byref(nch)], nch
+
+    @staticmethod
+    def gather_uniform(ids, n_frames, nodes_per_frame, edges_per_frame, src_tables, dst_tables, src_graph=None, dst_graph=None,
+                       chunk_row=None, call=None) -> int:
+        """the batch of the equal-sized frames ``ids`` in one launch, and its sorted graph with one more (fastegnn_collate_gather_uniform);
+        tables as ``gather``, graph arrays as ``graph`` (``dst_graph`` None: no graph).  ``call``: ``uniform_call``'s result for these very
+        tensors, which spares rebuilding the argument list.  Returns n_chunks (0 without a graph), which is host arithmetic."""
+        if not ids.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        from . import _lib as K
+        from .model import _stream
+        args, nch = call if call is not None else HipCollateOps.uniform_call(ids, n_frames, nodes_per_frame, edges_per_frame,
+                                                                             src_tables, dst_tables, src_graph, dst_graph, chunk_row)
+        K.check(K.lib().fastegnn_collate_gather_uniform(*args, _stream(ids.device)), "fastegnn_collate_gather_uniform")
         return nch.value
 
 
@@ -536,6 +580,15 @@ class PackedDataset:
     def __len__(self) -> int:
         return self.node_ptr_host.size - 1
 
+    @property
+    def frame_shape(self):
+        """``(nodes, edges)`` when every frame has the same node count and the same edge count (the N-body sets), else ``None``; from
+        the host copies of the counts.  What ``PackedStream`` needs."""
+        nodes, edges = int(self._node_cnt[0]), int(self._edge_cnt[0])
+        if (self._node_cnt == nodes).all() and (self._edge_cnt == edges).all():
+            return nodes, edges
+        return None
+
     def __getitem__(self, i: int) -> Frame:
         n = len(self)
         i = int(i)
@@ -636,3 +689,102 @@ class PackedLoader:
         for i in range(len(self)):
             a, b = i * self.batch_size, min((i + 1) * self.batch_size, n)
             yield self.packed._assemble(ids_dev[a:b], order_host[a:b], self.graphs)
+
+
+def _u64(v) -> int:
+    return int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+def _i64(v) -> int:
+    v = _u64(v)
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+class PackedStream:
+    """Batches of a ``PackedDataset`` whose frames all have the same node and edge counts (``packed.frame_shape``: the N-body sets),
+    with NO host work per batch.  Every full batch then has the same shapes, so the stream allocates ONCE -- every tensor of the
+    ``Batch`` (``ptr``, ``batch`` and the edge offsets never change and are written here), the frame numbers ``ids`` and, with
+    ``graphs`` (``None`` / ``"csr"`` / ``"csr+csc"`` / a callable ``n_edges -> bool`` evaluated once with ``B * edges``, as
+    ``PackedDataset.batch``), the arrays of one ``SortedGraph``; ``build_graphs()`` runs here.  The order is drawn on the device: a
+    keyed permutation of the frames per epoch (include/fastegnn_hip.h, fastegnn_collate_draw) from ``{seed, epoch, cursor}`` in device
+    memory -- not ``torch.randperm``'s order; ``shuffle=False`` walks the frames in order.
+
+    ``next()`` issues two launches on the current stream (three with a graph): the draw, one gather over every table (and graph
+    array), the graph's chunk rows.  It allocates nothing, uploads nothing, reads nothing back, and is the same launch sequence every
+    time, so it may be captured into a HIP graph; replays walk on through the epochs.  It returns the SAME ``Batch`` object each time,
+    its tensors overwritten: a batch is valid until the next ``next()``.  Whoever keeps an autograd graph, or any tensor of a batch,
+    across iterations holds data that the next batch replaces -- call ``backward()`` before the next ``next()`` (``train_step`` does)
+    or clone what must survive.  ``stream.ids`` is the device tensor of the current batch's frame numbers.
+
+    ``len(stream)`` is ``len(packed) // batch_size``: full batches only; under shuffle the frames left over differ per epoch, as with
+    ``DataLoader(drop_last=True)``.  Iterating yields ``len(stream)`` times ``next()``.  ``state_dict()`` / ``load_state_dict()`` hold
+    ``{seed, epoch, cursor}`` (reading them back is one synchronisation); a resumed stream continues the same sequence.  The batch has
+    ``collate``'s keys in ``collate``'s order, plus ``"graph"`` when asked: ``train_step`` / ``evaluate`` take it unchanged.  Ragged
+    datasets, and a short last batch, are ``PackedLoader``'s."""
+
+    def __init__(self, packed: PackedDataset, batch_size, shuffle=True, seed=0, graphs=None):
+        _check_graphs(graphs)
+        shape, n, B = packed.frame_shape, len(packed), int(batch_size)
+        if shape is None:
+            raise ValueError("PackedStream: the frames differ in their node or edge counts; a ragged dataset takes PackedLoader")
+        if B < 1 or B > n:
+            raise ValueError(f"PackedStream: batch_size = {B} with {n} frames: a stream yields full batches only (1 <= batch_size <= "
+                             f"frames); PackedLoader yields a short batch")
+        dev, T = packed.device, packed.tables
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fastegnn_amd.PackedStream: build the stream before the stream capture")
+        nodes, edges = shape
+        N, E = B * nodes, B * edges
+        self.packed, self.batch_size, self.shuffle, self.graphs = packed, B, bool(shuffle), graphs
+        self.frame_shape, self.device = shape, dev
+        out = {k: torch.zeros((N,) + T[k].shape[1:], dtype=torch.float32, device=dev) for k in _NODE_KEYS}
+        out["edge_attr"] = torch.zeros((E,) + T["edge_attr"].shape[1:], dtype=torch.float32, device=dev)
+        out["edge_index"] = torch.zeros((2, E), dtype=torch.int64, device=dev)
+        out["loc_mean"] = torch.zeros((B,) + T["loc_mean"].shape[1:], dtype=torch.float32, device=dev)
+        out["batch"] = torch.repeat_interleave(torch.arange(B, dtype=torch.int64), nodes).to(dev)
+        out["ptr"] = (torch.arange(B + 1, dtype=torch.int64) * nodes).to(dev)
+        self.edge_ptr = (torch.arange(B + 1, dtype=torch.int64) * edges).to(dev)
+        self.ids = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._state = torch.tensor([_i64(seed), 0, 0, 0], dtype=torch.int64).to(dev)   # the bit patterns of {seed, epoch, cursor, -}
+        self._src, self._dst = [T[k] for k in _PACK_KEYS], [out[k] for k in _PACK_KEYS]
+        self._src_graph = self._dst_graph = self._chunk_row = None
+        if graphs is not None:
+            from .model import SortedGraph
+            csc = bool(graphs(E)) if callable(graphs) else graphs == "csr+csc"
+            G = packed.build_graphs().graph_tables
+            i32 = dict(dtype=torch.int32, device=dev)
+            arr = [torch.zeros(N + 1, **i32)] + [torch.zeros(max(E, 1), **i32) for _ in range(3)]   # rowptr, erow, col, perm
+            arr += [torch.zeros(N + 1, **i32), torch.zeros(max(E, 1), **i32)] if csc else [None, None]
+            self._chunk_row = torch.zeros(E // _chunk_edges() + 2, **i32)   # fastegnn_chunk_rows(E)
+            self._src_graph, self._dst_graph = [G[k] for k in _GRAPH_KEYS], arr
+            out["graph"] = SortedGraph.from_arrays(*arr, self._chunk_row, E // _chunk_edges() + 1, N, N, E)
+        self._batch = Batch(**out)
+        self._call = None
+        if dev.type == "cuda":   # the argument list of the gather never changes: the buffers stay where they are
+            self._call = HipCollateOps.uniform_call(self.ids, n, nodes, edges, self._src, self._dst, self._src_graph, self._dst_graph,
+                                                    self._chunk_row)
+
+    def __len__(self) -> int:
+        return len(self.packed) // self.batch_size
+
+    def next(self) -> Batch:
+        """draws the next batch's frames and assembles them into the stream's buffers -> the stream's one ``Batch`` (see the class)"""
+        ops, (nodes, edges) = _COLLATE_OPS, self.frame_shape
+        ops.draw(self._state, self.batch_size, len(self.packed), self.shuffle, True, self.ids)
+        ops.gather_uniform(self.ids, len(self.packed), nodes, edges, self._src, self._dst, self._src_graph, self._dst_graph,
+                           self._chunk_row, call=self._call if ops is HipCollateOps else None)
+        return self._batch
+
+    def __iter__(self) -> Iterator[Batch]:
+        for _ in range(len(self)):
+            yield self.next()
+
+    def state_dict(self) -> dict:
+        """(copies the words back: one synchronisation)"""
+        seed, epoch, cursor, _ = self._state.tolist()
+        return {"seed": _u64(seed), "epoch": _u64(epoch), "cursor": _u64(cursor)}
+
+    def load_state_dict(self, state) -> None:
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fastegnn_amd.PackedStream: the state is written between replays, not inside a stream capture")
+        self._state[:3].copy_(torch.tensor([_i64(state["seed"]), _i64(state["epoch"]), _i64(state["cursor"])], dtype=torch.int64))

@@ -461,3 +461,27 @@ def evaluate(model, loader, sigma, weight, *, sampler: Optional[MMDSampler] = No
     finally:
         model.train(was_training)
     return dict(mse=host[0] / host[2], loss=host[1] / host[2], graphs=int(host[2]))
+
+
+def train_epoch(model, optimizer: FusedAdam, loader, sigma, weight, *, sampler: Optional[MMDSampler] = None,
+                num_sample: Optional[int] = None, sample_nodes=None) -> dict:
+    """The reference's ``train_single_epoch(..., backprop=True)`` (utils/train.py:23-179: its training epoch) -> ``dict(mse=, loss=,
+    graphs=)``.  The model is put into ``train()`` and every batch of ``loader`` -- a ``DataLoader``, ``PackedLoader`` or ``PackedStream``:
+    anything that yields the batches ``train_step`` takes -- runs one ``train_step`` with the arguments given here.  Each step's
+    ``(loss, mse)`` is added into three fp64 words on the device, weighted by the batch's graph count ``data['loc_mean'].size(0)``
+    (fastegnn_loss_accumulate; the words of ``mse_mmd_eval``): ONE read-back, after the last batch, where a hand-written loop pays
+    one ``.item()`` per batch to log its loss.  ``mse`` is the graph-weighted mean MSE of the epoch, the number the reference prints;
+    ``loss`` the same mean of the full objective.  An empty loader returns NaNs and ``graphs=0``, like ``evaluate``."""
+    model.train()
+    acc = None
+    for data in loader:
+        loss, mse = train_step(model, optimizer, data, sample_nodes, sigma, weight, sampler=sampler, num_sample=num_sample)
+        dev = loss.device
+        if acc is None:
+            acc = torch.zeros(3, dtype=torch.float64, device=dev)
+        K.check(K.lib().fastegnn_loss_accumulate(K.ptr(loss), K.ptr(mse), data["loc_mean"].size(0), K.ptr(acc), _stream(dev)),
+                "fastegnn_loss_accumulate")
+    if acc is None:
+        return dict(mse=float("nan"), loss=float("nan"), graphs=0)
+    host = acc.tolist()   # the one synchronisation of the epoch
+    return dict(mse=host[0] / host[2], loss=host[1] / host[2], graphs=int(host[2]))

@@ -507,6 +507,13 @@ int fastegnn_loss_mse_mmd_ragged(const float *loc_pred, const float *loc_t, cons
 int fastegnn_loss_mse_mmd_eval(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
                                const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
                                float weight, double *acc, void *stream);
+/* The same three words for a TRAINING epoch (utils/train.py:23-179 with backprop=True), from the two numbers a training step has
+ * already computed.  ADDITIVE export, found by symbol: FASTEGNN_ABI_VERSION stays 108.
+ *   loss, mse  DEVICE float: the step's objective and its plain MSE (fastegnn_loss_mse_mmd's loss2[0] and loss2[1])
+ *   acc[0] += B * *mse,  acc[1] += B * *loss,  acc[2] += B       in fp64, by one thread (B * an fp32 value is exact in fp64)
+ * so that an epoch's graph-weighted means cost ONE read-back after its last step.  Reads nothing back, synchronises nothing,
+ * capturable.  B == 0 launches nothing.  FASTEGNN_E_INVALID before any launch for: a null pointer, B < 0. */
+int fastegnn_loss_accumulate(const float *loss, const float *mse, int32_t B, double *acc, void *stream);
 
 /* ---- graph construction on device (datasets/simulation/dataset.py:80,96-101) ----
  * radius graph without self loops: all ordered pairs (i, j != i) with |x_i - x_j|^2 <= r^2 (fp32, each
@@ -631,6 +638,56 @@ int fastegnn_collate_graph(const int64_t *ids, int32_t B, const int64_t *src_nod
                            const int32_t *g_col, const int32_t *g_perm, const int64_t *g_cscptr, const int32_t *g_csc_eid,
                            int32_t *rowptr, int32_t *erow, int32_t *col, int32_t *perm, int32_t *cscptr, int32_t *csc_eid,
                            int32_t *chunk_row, int32_t *n_chunks, void *stream);
+
+/* ---- streaming a packed dataset of EQUAL-SIZED frames (the N-body sets: every frame n particles and the same top-k pairs) ----
+ * ADDITIVE exports, found by symbol: FASTEGNN_ABI_VERSION stays 108.  When every frame holds nodes_per_frame nodes and
+ * edges_per_frame edges, every full batch has the same shapes and a frame's place in a table is a multiplication: the batch lives in
+ * buffers allocated once, its order is drawn on the device, and a batch is two launches (three with its sorted graph) that are the
+ * same every time.  Neither call reads anything back, synchronises or allocates; both are capturable.
+ *
+ * _draw  the frame numbers of the next batch.  state DEVICE uint64[4] = {seed, epoch, cursor, reserved}.  With nb = n_frames / B
+ *   (full batches only; the n_frames % B frames left over differ per epoch under shuffle) and c = cursor % nb:
+ *     ids_out[i] = perm(c * B + i)   for i < B
+ *   shuffle == 0: perm is the identity.  Otherwise perm is perm_b of fastegnn_mmd_sample above, bit for bit (mix64, mix32, eight
+ *   Feistel rounds over 2^k >= n_frames, cycle walking), with n := n_frames, counter := epoch and b := 0x5354524D -- a fixed tag, so
+ *   that a stream and an MMD sampler with equal seeds do not draw with the same keys.  One epoch visits nb * B distinct frames.
+ *   advance != 0: after every id is written, cursor = c + 1; when that reaches nb, cursor = 0 and epoch += 1.  ONE launch of one
+ *   workgroup: every thread reads the state, a workgroup barrier follows the last id (rounds of 1024 ids for larger B), then thread
+ *   0 writes the two words -- a draw sees one consistent state, and replays of a captured draw walk on through the epochs.
+ *   Whatever the state words hold, every id written is in [0, n_frames).  `reserved` is neither read nor written.
+ *   FASTEGNN_E_INVALID before any launch for: a null pointer, B < 1, n_frames < B.
+ *
+ * _gather_uniform  the batch of the B frames ids[0 .. B) in ONE launch over a job table: no offset arrays, no binary search, no
+ *   plan launch.  src_tables / dst_tables / widths as fastegnn_collate_gather; src_nodes / src_edges must equal n_frames *
+ *   nodes_per_frame / n_frames * edges_per_frame.  Element e of a table with w floats per row and `count` rows per frame belongs
+ *   to batch slot f = e / (count * w); its source element is clamp(ids[f]) * count * w + (e - f * count * w), the id clamped to
+ *   [0, n_frames).  LOC_MEAN has one row per frame.  EDGE_INDEX (int64 [2, B * edges_per_frame], row r of the source at
+ *   r * src_edges) adds f * nodes_per_frame.  `ptr`, `batch` and the edge offsets of the batch are NOT written: they never change
+ *   for a uniform stream and the caller writes them once.
+ *   With rowptr != NULL the same launch assembles the batch's sorted graph from the six packed tables of fastegnn_collate_graph,
+ *   by its formulas with no = f * nodes_per_frame, eo = f * edges_per_frame and src_edge_ptr[j] = j * edges_per_frame;
+ *   rowptr[B * nodes_per_frame] = cscptr[..] = B * edges_per_frame; a second launch (the chunk launch of fastegnn_build_csr)
+ *   writes chunk_row, and *n_chunks (HOST int) = B * edges_per_frame / fastegnn_chunk_edges() + 1.  cscptr / csc_eid both NULL: no
+ *   col-keyed index.  rowptr == NULL: no graph, the graph arguments are not looked at and *n_chunks is not written.
+ *   edges_per_frame == 0: the edge jobs take no part, rowptr / cscptr are all zero and chunk_row is the one-chunk form.
+ *   Access width, chosen per job on the host: 16 bytes per lane when the job's per-frame segment length in bytes and both base
+ *   addresses are multiples of 16, 8 bytes when they are multiples of 8, else one element per lane (row 1 of a packed edge_index
+ *   is 16-byte aligned only when src_edges is even); the int64 -> int32 pointer jobs are one element per lane.  A lane's vector
+ *   never straddles two frames.  Several loads are in flight before the stores; beyond the block cap the workgroups stride over
+ *   the tiles.  The safety contract of _gather holds: ids clamped, nothing read outside the packed tables, nothing written beyond
+ *   B * the counts, whatever ids holds.
+ *   FASTEGNN_E_INVALID before any launch for: B < 1, n_frames < 1, a negative count, src_nodes / src_edges that are not n_frames
+ *   times the counts, a width outside 0 .. 2^20, a null pointer that would be used, a batch beyond the int32 sizes of build_csr
+ *   when a graph is asked for, cscptr without csc_eid or the reverse, a col-keyed index asked for with edges but no g_cscptr /
+ *   g_csc_eid.  The packed graph tables are looked at only when edges_per_frame > 0 (a dataset without edges holds empty ones). */
+int fastegnn_collate_draw(uint64_t *state, int32_t B, int32_t n_frames, int32_t shuffle, int32_t advance, int64_t *ids_out,
+                          void *stream);
+int fastegnn_collate_gather_uniform(const int64_t *ids, int32_t B, int32_t n_frames, int64_t nodes_per_frame,
+                                    int64_t edges_per_frame, int64_t src_nodes, int64_t src_edges, const void *const *src_tables,
+                                    void *const *dst_tables, const int32_t *widths, const int64_t *g_rowptr, const int32_t *g_erow,
+                                    const int32_t *g_col, const int32_t *g_perm, const int64_t *g_cscptr, const int32_t *g_csc_eid,
+                                    int32_t *rowptr, int32_t *erow, int32_t *col, int32_t *perm, int32_t *cscptr, int32_t *csc_eid,
+                                    int32_t *chunk_row, int32_t *n_chunks, void *stream);
 
 /* ---- exchange steps of the sharded path (the reference has no distributed code) ----
  * RCCL collectives behind the C ABI: every call is enqueued on `stream` (ordered with the stage kernels, capturable

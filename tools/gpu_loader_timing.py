@@ -8,7 +8,10 @@ at batch size 20.  The batches of the two loaders are compared with torch.equal 
 PackedLoader(graphs=model.deterministic_for), hands every batch over with its sorted graph assembled from indices sorted once
 (PackedDataset.build_graphs), so that train_step sorts nothing: its graphs are compared with the model's own first, and it
 alternates with the other two.  Prints what profiles/packed_loader_graphs.txt holds (profiles/packed_loader.txt: the same without
-the third loader).
+the third loader).  At the two N-body shapes, whose frames are equal-sized, a fourth loader alternates with them:
+data.PackedStream(graphs=model.deterministic_for) -- static buffers, the order drawn on the device, three launches per batch -- whose
+yardstick is the third loader in the same call; its gather (+ chunk launch) is timed under the library's events against the third
+loader's gather + graph launches and a copy_ of the same bytes (profiles/packed_stream.txt).
 
     python tools/gpu_loader_timing.py [output file]
 """
@@ -78,6 +81,67 @@ def gather_kernel_us(packed, ids, runs=20):
     K.lib().fastegnn_profile_enable(0)
     ms, n = K.profile_collect()["misc"]
     return ms / n * 1e3, n
+
+
+def _misc_us(call, runs):
+    """`runs` calls of `call` under the library's per-launch HIP events -> (microseconds per call, event pairs counted)"""
+    from fastegnn_amd import _lib as K
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    K.lib().fastegnn_profile_enable(1)
+    K.profile_collect()
+    for _ in range(runs):
+        call()
+    K.lib().fastegnn_profile_enable(0)
+    ms, n = K.profile_collect()["misc"]
+    return ms / runs * 1e3, n
+
+
+def _graph_arrays(g):
+    return [g.rowptr, g.erow, g.col, g.perm, g.cscptr, g.csc_eid]
+
+
+def _batch_bytes(batch):
+    """bytes read + written by the assembly of a batch with its graph: every output once in, once out (ptr / batch are written only
+    by the ragged gather and not at all by the uniform one: left out on both sides); rowptr / cscptr are read as int64"""
+    out = sum(batch[k].numel() * batch[k].element_size() for k in D._PACK_KEYS)
+    arrays = [a for a in _graph_arrays(batch["graph"]) if a is not None]
+    out += sum(a.numel() * 4 for a in arrays)
+    extra = sum(a.numel() * 4 for a in (batch["graph"].rowptr, batch["graph"].cscptr) if a is not None)
+    return 2 * out + extra
+
+
+def ragged_gather_graph_us(packed, ids, graphs, runs=20):
+    """PackedLoader's gather + graph launches of one batch (outputs allocated once, the plan run once) -> (us per batch, event pairs)"""
+    b = packed.batch(ids, graphs=graphs)
+    ids_dev, g = ids.cuda(), b["graph"]
+    edge_ptr = torch.empty_like(b["ptr"])
+    ops, T, G = D._COLLATE_OPS, packed.tables, packed.graph_tables
+    ops.plan(ids_dev, packed.node_ptr, packed.edge_ptr, b["ptr"], edge_ptr)
+    n_edges = b["edge_index"].size(1)
+
+    def call():
+        ops.gather(ids_dev, packed.node_ptr, packed.edge_ptr, b["ptr"], edge_ptr, [T[k] for k in D._PACK_KEYS],
+                   [b[k] for k in D._PACK_KEYS], b["batch"])
+        ops.graph(ids_dev, packed.node_ptr, packed.edge_ptr, b["ptr"], edge_ptr, b.num_nodes, n_edges, [G[k] for k in D._GRAPH_KEYS],
+                  _graph_arrays(g), g.chunk_row)
+    return _misc_us(call, runs)
+
+
+def uniform_gather_us(stream, runs=20):
+    """PackedStream's gather + chunk launches of one batch, the ids of its latest draw -> (us per batch, event pairs)"""
+    nodes, edges = stream.frame_shape
+    stream.next()
+
+    def call():
+        D._COLLATE_OPS.gather_uniform(stream.ids, len(stream.packed), nodes, edges, stream._src, stream._dst, stream._src_graph,
+                                      stream._dst_graph, stream._chunk_row, call=stream._call)
+    return _misc_us(call, runs)
+
+
+def spread(ts):
+    return f"[{min(ts) * 1e3:.3f} .. {max(ts) * 1e3:.3f}] ms"
 
 
 def copy_us(nbytes, runs=20):
@@ -175,16 +239,41 @@ def main():
                    f"col-keyed index in the first batch: {model.deterministic_for(first['edge_index'].size(1))}; assembled graphs "
                    f"equal the model's own (torch.equal, every array, every batch): {same_g}")
         loaders = [("DataLoader", old), ("PackedLoader", new), ("Packed+graph", gl)]
+        stream = None
+        if packed.frame_shape is not None:   # equal-sized frames: the stream, with the graph the third loader carries
+            stream = D.PackedStream(packed, bs, shuffle=True, seed=9, graphs=model.deterministic_for)
+            loaders.append(("PackedStream", stream))
+            sb = stream.next()
+            want = D.collate([packed[int(i)] for i in stream.ids.tolist()])
+            same_s = all(torch.equal(sb[k], want[k]) for k in want.keys())
+            wg, got = model.sorted_graph(sb["edge_index"], sb.num_nodes), sb["graph"]
+            same_s &= all(torch.equal(getattr(got, k), getattr(wg, k)) for k in arrays if getattr(wg, k) is not None)
+            model._graph_cache.clear()
+            nbytes = _batch_bytes(sb)
+            us_u, n_u = uniform_gather_us(stream)
+            us_r, n_r = ragged_gather_graph_us(packed, ids, model.deterministic_for)
+            out.append(f"  PackedStream: {len(stream)} full batches per epoch; its batch equals collate of its ids and its graph the model's "
+                       f"own (torch.equal): {same_s}")
+            out.append(f"  one batch with its graph, {nbytes / 1e6:.2f} MB read + written, the library's event pairs (mean of 20 batches): "
+                       f"uniform gather + chunk launch {us_u:.1f} us ({n_u} pairs) = {nbytes / us_u / 1e3:.0f} GB/s;  PackedLoader's gather + graph "
+                       f"launches {us_r:.1f} us ({n_r} pairs) = {nbytes / us_r / 1e3:.0f} GB/s;  a torch copy_ of the same bytes: "
+                       f"{nbytes / copy_us(nbytes // 2) / 1e3:.0f} GB/s")
         out.append("  loader alone:")
         ts = epoch_times(loaders, lambda batch: None)
         out += [line(k, ts[k], nb) for k, _ in loaders]
+        if stream is not None:
+            below = max(ts["PackedStream"]) < min(ts["Packed+graph"])
+            out.append(f"    PackedStream {spread(ts['PackedStream'])} against Packed+graph {spread(ts['Packed+graph'])}: wholly below: {below}")
         opt = FusedAdam(model.parameters(), lr=5e-4, weight_decay=1e-12)
         smp = MMDSampler(0)
         out.append("  loader + train_step (FastEGNN hidden 64, 4 layers, C = 3, device-side MMD sample):")
         ts = epoch_times(loaders, lambda batch: train_step(model, opt, batch, None, sigma=1.0, weight=0.01, sampler=smp,
                                                            num_sample=3 * C))
         out += [line(k, ts[k], nb) for k, _ in loaders]
-        del frames, packed, old, new, gl, model, opt
+        if stream is not None:
+            below = max(ts["PackedStream"]) < min(ts["Packed+graph"])
+            out.append(f"    PackedStream {spread(ts['PackedStream'])} against Packed+graph {spread(ts['Packed+graph'])}: wholly below: {below}")
+        del frames, packed, old, new, gl, stream, model, opt
         torch.cuda.empty_cache()
     text = "\n".join(out)
     print(text)
