@@ -228,10 +228,13 @@ int fastegnn_layer_forward(const fastegnn_layer_t *L, void *stream) {
     if ((rc = edge_forward(L, st))) return rc;
     return virt_forward(L, st);
   }
-  if ((rc = graph_xsum(L, st))) return rc;
-  if ((rc = graph_pre_forward(L, st))) return rc;
+  // S2 in two launches: the block partials of x wait in aggm (the edge stage writes it later), graph_pre combines them into
+  // xsum and zeroes the pools of the virtual stage
+  FE_REQUIRE(L->aggm, "fastegnn_layer_forward: aggm null");
+  if ((rc = graph_xsum_partials(L, L->aggm, st))) return rc;
+  if ((rc = graph_pre_forward(L, st, L->aggm))) return rc;
   if ((rc = edge_forward(L, st))) return rc;
-  if ((rc = virt_forward(L, st))) return rc;
+  if ((rc = virt_forward(L, st, true))) return rc;
   return graph_post_forward(L, st);
 }
 
@@ -259,9 +262,9 @@ int fastegnn_layer_backward(const fastegnn_layer_t *L, void *stream) {
     if ((rc = node_pre_backward(L, st, &wb))) return rc;
     return wb.finish();
   }
-  if ((rc = graph_post_backward(L, st, &wb))) return rc;
+  if ((rc = graph_post_backward(L, st, &wb, true))) return rc;   // (+ the zeroing of g_Bc / g_Zp for the virtual stage)
   if ((rc = guard_virt())) return rc;
-  if ((rc = virt_backward(L, st, &wb))) return rc;
+  if ((rc = virt_backward(L, st, &wb, true))) return rc;
   if ((rc = guard_stage(L, wb, G_GRAPH_PRE))) return rc;
   if ((rc = graph_pre_backward(L, st, &wb))) return rc;
   if ((rc = guard_edge())) return rc;

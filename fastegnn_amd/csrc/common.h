@@ -360,6 +360,31 @@ __device__ __forceinline__ void gemm64(const float *img, const Vec &in, Vec &acc
   }
 }
 
+// gemm64 dealt to the four waves of a workgroup (the per-graph stages: ONE tile of 16 rows, latency is all there is): wave t
+// computes the output features [16t, 16t + 16) -- acc is the t-th block of gemm64's accumulator, the MFMAs of that block in gemm64's
+// order, hence the same bits -- from its four fragments of the image, which gemm64_frags requests ahead of the chain of products.
+__device__ __forceinline__ void gemm64_frags(const float *img, int t, f32x4 frag[4]) {
+  const f32x4 *ip = reinterpret_cast<const f32x4 *>(img) + lane_id();
+#pragma unroll
+  for (int tp = 0; tp < 4; ++tp) frag[tp] = ip[(t * 4 + tp) * 64];
+}
+__device__ __forceinline__ void gemm64_block(const f32x4 frag[4], const Vec &in, f32x4 &acc) {
+#pragma unroll
+  for (int tp = 0; tp < 4; ++tp)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(frag[tp][r], in.t[tp][r], acc, 0, 0, 0);
+}
+// block t of a 64-vector / of a row in the D layout (vload_vec(w, q).t[t])
+__device__ __forceinline__ f32x4 vload_block(const float *w, int t, int q) { return *reinterpret_cast<const f32x4 *>(w + 16 * t + 4 * q); }
+__device__ __forceinline__ void vstore_block(float *row, int t, int q, const f32x4 &v) { *reinterpret_cast<f32x4 *>(row + 16 * t + 4 * q) = v; }
+// an element-wise Vec function applied to one block
+template <class F>
+__device__ __forceinline__ f32x4 vblock(const f32x4 &x, F f) {
+  Vec v;
+  v.t[0] = v.t[1] = v.t[2] = v.t[3] = x;
+  return f(v).t[0];
+}
+
 // ---- 3-way bf16 split ("bf16x3") variant of gemm64 ------------------------------------------
 // fp32-input MFMA shares the vector ALUs with every other VALU instruction and runs at 1/16 of the
 // bf16 matrix rate.  x = h + m + l with h, m, l bf16 values (8+8+8 mantissa bits, each the round-to-nearest

@@ -98,14 +98,19 @@ int pack_weights(const fastegnn_layer_t *L, hipStream_t st);
 int pack_weights_all(const fastegnn_layer_t *const *layers, int n, hipStream_t st);
 int node_pre_forward(const fastegnn_layer_t *L, hipStream_t st);
 int graph_xsum(const fastegnn_layer_t *L, hipStream_t st);
-int graph_pre_forward(const fastegnn_layer_t *L, hipStream_t st);
+// The layer call folds the small launches of S2 (layer_fwd.hip, S2a): graph_xsum_partials leaves the block partials of x in
+// `part`, graph_pre_forward(part != null) combines them into L->xsum itself and zeroes poolV / poolX for virt_forward(pools_zeroed).
+int graph_xsum_partials(const fastegnn_layer_t *L, float *part, hipStream_t st);
+int graph_pre_forward(const fastegnn_layer_t *L, hipStream_t st, float *part = nullptr);
 int edge_forward(const fastegnn_layer_t *L, hipStream_t st);
-int virt_forward(const fastegnn_layer_t *L, hipStream_t st);
+int virt_forward(const fastegnn_layer_t *L, hipStream_t st, bool pools_zeroed = false);
 int graph_post_forward(const fastegnn_layer_t *L, hipStream_t st);
 // `shared`: a weight-gradient batch that outlives the stage (fastegnn_layer_backward: ONE contraction launch and ONE
 // reduction launch per layer instead of one pair per stage); null: the stage contracts and reduces its own jobs.
-int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr);
-int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr);
+// zero_acc: the stage also zeroes g_Bc / g_Zp, the accumulators of the virtual stage that follows it in the layer call
+// (virt_backward(acc_zeroed) then issues no fills of its own)
+int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, bool zero_acc = false);
+int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, bool acc_zeroed = false);
 int graph_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr);
 int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr);
 // virt_bwd.hip: floats of wg_virt for B4 (1 <= C <= 64)

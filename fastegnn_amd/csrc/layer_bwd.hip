@@ -32,13 +32,25 @@ struct GraphPostBwdArgs {
   float *g_Z, *g_HvT, *g_poolV, *g_poolX, *wg_u, *wg_gz5, *wg_pm;
   int B, C, flags;
   float act_param = 0.f;
+  float *z_Bc = nullptr, *z_Zp = nullptr;   // non-null: zeroed here ([B,C,H] / [B,3,C]: the accumulators of the virtual stage)
 };
+// the layer call: g_Bc / g_Zp of the virtual stage, which runs next on the stream, are zeroed by this stage's launch
+__device__ __forceinline__ void zero_virt_acc(float *z_Bc, float *z_Zp, int B, int C) {
+  const int i0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  if (z_Bc) for (int i = i0; i < B * C * H; i += step) z_Bc[i] = 0.f;
+  if (z_Zp) for (int i = i0; i < B * 3 * C; i += step) z_Zp[i] = 0.f;
+}
+// One workgroup per tile of 16 rows; the 64 output features of each of the five products are dealt to its four waves
+// (gemm64_block) and every wave requests its 20 weight fragments before the first product.  (One wave ran the five products one
+// after the other, each behind its own fragment loads from global memory: 17 us for the 16 rows of cfg4.)  g_z5, the one vector a
+// later product contracts over, is exchanged through LDS.
 __global__ __launch_bounds__(256) void graph_post_bwd_kernel(GraphPostBwdArgs a) {
   const bool bf = a.flags & FASTEGNN_F_BF16;   // bf16 operand mode: the B operand of every product is rounded
   auto rb = [&](const Vec &v) { return bf ? vround(v) : v; };
-  const int l = lane_id(), j = l & 15, q = l >> 4;
-  const int wave = global_wave_id(), nwaves = (gridDim.x * blockDim.x) >> 6;
+  __shared__ __attribute__((aligned(16))) float xt[16 * TS];
+  const int l = lane_id(), j = l & 15, q = l >> 4, w = wave_id();
   const int M = a.B * a.C, ntiles = (M + 15) >> 4;
+  zero_virt_acc(a.z_Bc, a.z_Zp, a.B, a.C);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.B * 3 * a.C; i += gridDim.x * blockDim.x) {
     const int b = i / (3 * a.C);
     const float g = a.g_Z_out[i];
@@ -52,7 +64,14 @@ __global__ __launch_bounds__(256) void graph_post_bwd_kernel(GraphPostBwdArgs a)
     }
     return;
   }
-  for (int tile = wave; tile < ntiles; tile += nwaves) {
+  f32x4 f5a[4], f5b[4], f6t[4], f5at[4], f5bt[4];
+  gemm64_frags(a.wpack + (size_t)I_W5A * IMG, w, f5a);
+  gemm64_frags(a.wpack + (size_t)I_W5B * IMG, w, f5b);
+  gemm64_frags(a.wpack + (size_t)I_W6T * IMG, w, f6t);
+  gemm64_frags(a.wpack + (size_t)I_W5AT * IMG, w, f5at);
+  gemm64_frags(a.wpack + (size_t)I_W5BT * IMG, w, f5bt);
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int m = tile * 16 + j;
     const bool valid = m < M;
     const int mc = valid ? m : M - 1;
@@ -60,24 +79,31 @@ __global__ __launch_bounds__(256) void graph_post_bwd_kernel(GraphPostBwdArgs a)
     const float inv = 1.0f / fmaxf(a.xsum[b * 4 + 3], 1.f);
     const Vec hv = vload_row(a.HvT + (size_t)mc * H, q);
     const Vec pm = vscale(vload_row(a.poolV + (size_t)mc * H, q), inv);
-    Vec z5 = vload_vec(a.b5, q);
-    gemm64(a.wpack + (size_t)I_W5A * IMG, rb(hv), z5);
-    gemm64(a.wpack + (size_t)I_W5B * IMG, rb(pm), z5);
     const Vec g_out = vload_row(a.g_HvT_out + (size_t)mc * H, q);
-    Vec g_u = vzero();
-    gemm64(a.wpack + (size_t)I_W6T * IMG, rb(g_out), g_u);
-    const Vec g_z5 = vdsilu_mul(g_u, z5 FE_ACT(a));
-    Vec g_hv = (a.flags & FASTEGNN_F_RESIDUAL) ? g_out : vzero();
-    gemm64(a.wpack + (size_t)I_W5AT * IMG, rb(g_z5), g_hv);
-    Vec g_pm = vzero();
-    gemm64(a.wpack + (size_t)I_W5BT * IMG, rb(g_z5), g_pm);
+    f32x4 z5 = vload_block(a.b5, w, q);
+    gemm64_block(f5a, rb(hv), z5);
+    gemm64_block(f5b, rb(pm), z5);
+    f32x4 g_u = zero4;
+    gemm64_block(f6t, rb(g_out), g_u);
+    Vec Z, G;
+    Z.t[0] = Z.t[1] = Z.t[2] = Z.t[3] = z5;
+    G.t[0] = G.t[1] = G.t[2] = G.t[3] = g_u;
+    const f32x4 g_z5w = vdsilu_mul(G, Z FE_ACT(a)).t[0];
+    vstore_block(xt + j * TS, w, q, g_z5w);
+    __syncthreads();
+    const Vec g_z5 = rb(vload_row(xt + j * TS, q));
+    f32x4 g_hv = (a.flags & FASTEGNN_F_RESIDUAL) ? vload_block(a.g_HvT_out + (size_t)mc * H, w, q) : zero4;
+    gemm64_block(f5at, g_z5, g_hv);
+    f32x4 g_pm = zero4;
+    gemm64_block(f5bt, g_z5, g_pm);
     if (valid) {
-      vstore_row(a.wg_u + (size_t)m * H, q, vsilu(z5 FE_ACT(a)));
-      vstore_row(a.wg_gz5 + (size_t)m * H, q, g_z5);
-      vstore_row(a.wg_pm + (size_t)m * H, q, pm);
-      vstore_row(a.g_HvT + (size_t)m * H, q, g_hv);
-      vstore_row(a.g_poolV + (size_t)m * H, q, vscale(g_pm, inv));
+      vstore_block(a.wg_u + (size_t)m * H, w, q, vblock(z5, [&](const Vec &v) { return vsilu(v FE_ACT(a)); }));
+      vstore_block(a.wg_gz5 + (size_t)m * H, w, q, g_z5w);
+      vstore_block(a.wg_pm + (size_t)m * H, w, q, vload_block(a.poolV + (size_t)mc * H, w, q) * inv);
+      vstore_block(a.g_HvT + (size_t)m * H, w, q, g_hv);
+      vstore_block(a.g_poolV + (size_t)m * H, w, q, g_pm * inv);
     }
+    __syncthreads();   // xt is rewritten by the next tile
   }
 }
 
@@ -85,7 +111,8 @@ __global__ __launch_bounds__(256) void graph_post_bwd_kernel(GraphPostBwdArgs a)
 // coordinate part alone (the same expressions as above); g_HvT starts from zero (graph_pre_bwd adds the g_Bc part), g_poolV is zero and
 // not written: the virtual stage does not read it then
 __global__ __launch_bounds__(256) void graph_post_bwd_coords_kernel(const float *xsum, const float *g_Z_out, float *g_Z, float *g_poolX,
-                                                                    float *g_HvT, int B, int C) {
+                                                                    float *g_HvT, int B, int C, float *z_Bc, float *z_Zp) {
+  zero_virt_acc(z_Bc, z_Zp, B, C);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 3 * C; i += gridDim.x * blockDim.x) {
     const int b = i / (3 * C);
     const float g = g_Z_out[i];
@@ -95,14 +122,16 @@ __global__ __launch_bounds__(256) void graph_post_bwd_coords_kernel(const float 
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * C * H; i += gridDim.x * blockDim.x) g_HvT[i] = 0.f;
 }
 
-int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared) {
+int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, bool zero_acc) {
+  FE_REQUIRE(!zero_acc || (L->g_Bc && L->g_Zp), "graph_post_backward: g_Bc / g_Zp null");
+  float *z_Bc = zero_acc ? L->g_Bc : nullptr, *z_Zp = zero_acc ? L->g_Zp : nullptr;
   if (!L->g_HvT_out && !has(L, FASTEGNN_F_RF)) {
     FE_REQUIRE(!L->g_h_out, "graph_post_backward: g_HvT_out is null and g_h_out is not (both null: no gradient for h / Hv; otherwise neither)");
     FE_REQUIRE(L->xsum && L->g_Z_out && L->g_Z && L->g_HvT && L->g_poolX, "graph_post_backward: null buffer");
     int grid = cdiv((long)L->B * L->C * H, 256);
     if (grid > 256) grid = 256;
     if (grid < 1) grid = 1;
-    { ProfScope _ps_graph_post_bwd_kernel(K_GRAPH_POST_BWD, st); hipLaunchKernelGGL(graph_post_bwd_coords_kernel, dim3(grid), dim3(256), 0, st, L->xsum, L->g_Z_out, L->g_Z, L->g_poolX, L->g_HvT, L->B, L->C); }
+    { ProfScope _ps_graph_post_bwd_kernel(K_GRAPH_POST_BWD, st); hipLaunchKernelGGL(graph_post_bwd_coords_kernel, dim3(grid), dim3(256), 0, st, L->xsum, L->g_Z_out, L->g_Z, L->g_poolX, L->g_HvT, L->B, L->C, z_Bc, z_Zp); }
     return check_launch("graph_post_bwd_coords_kernel");   // no node_mlp_virtual jobs: their gradients are not defined
   }
   FE_REQUIRE(L->xsum && L->HvT && L->poolV && L->g_Z_out && L->g_HvT_out && L->g_Z && L->g_HvT && L->g_poolV &&
@@ -112,8 +141,8 @@ int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *s
   float *wg_gp = L->wg_node + 4 * wg_node_rows(L) * H;   // this stage's operand region of wg_node (kernels.h)
   float *wg_u = wg_gp, *wg_gz5 = wg_gp + M * H, *wg_pm = wg_gp + 2 * M * H;
   GraphPostBwdArgs a{L->xsum, L->HvT, L->poolV, L->g_Z_out, L->g_HvT_out, L->wpack, L->params[FASTEGNN_P_NODEV0_B],
-                     L->g_Z, L->g_HvT, L->g_poolV, L->g_poolX, wg_u, wg_gz5, wg_pm, L->B, L->C, L->flags, L->act_param};
-  int grid = cdiv(cdiv(M, 16), 4);
+                     L->g_Z, L->g_HvT, L->g_poolV, L->g_poolX, wg_u, wg_gz5, wg_pm, L->B, L->C, L->flags, L->act_param, z_Bc, z_Zp};
+  int grid = cdiv(M, 16);   // one workgroup per tile
   if (grid > 256) grid = 256;
   if (grid < 1) grid = 1;
   { ProfScope _ps_graph_post_bwd_kernel(K_GRAPH_POST_BWD, st); hipLaunchKernelGGL(graph_post_bwd_kernel, dim3(grid), dim3(256), 0, st, a); }
@@ -143,8 +172,14 @@ struct GraphPreBwdArgs {
   int B, C, bf16;
 };
 // grid (B, GPB_SPLIT): the per-(channel, feature) outputs of a graph are dealt to GPB_SPLIT workgroups; each of them
-// recomputes the graph's small matrices (mz, g_mX, g_mz), workgroup 0 writes the centroid gradient
+// recomputes the graph's small matrices (mz, g_mX, g_mz), workgroup 0 writes the centroid gradient.
+// The graph's g_Bc rows and the V1b / V1d blocks of edge_mlp_virtual.0.weight are staged in LDS with coalesced loads first, all of
+// them in flight together: the g_mX loop read g_Bc and V1d from global memory with one lane per (c', c) -- g_Bc at a stride of a row
+// per lane, V1d at the weight's row stride of 2H + 1 + C floats -- and the g_HvT loop went to global memory for V1b[o][k] and
+// g_Bc[o] once per o, a chain of load round trips.  The sums keep their order.
 constexpr int GPB_SPLIT = 4;
+constexpr int GPB_GLD = H + 1;   // row stride of the g_Bc rows in LDS: lanes along c hit different banks
+static size_t graph_pre_bwd_lds_floats(int C) { return (size_t)6 * C + C * C + (size_t)C * GPB_GLD + (size_t)H * (C + 1) + H * H; }
 __global__ __launch_bounds__(256) void graph_pre_bwd_kernel(GraphPreBwdArgs a) {
   extern __shared__ float sm[];
   const int C = a.C, b = blockIdx.x, ld = 2 * H + 1 + C;
@@ -152,6 +187,12 @@ __global__ __launch_bounds__(256) void graph_pre_bwd_kernel(GraphPreBwdArgs a) {
   float *mz = sm;               // [3][C]
   float *gmX = sm + 3 * C;      // [C][C]  d/d mX[c'][c] stored at [c'*C + c]
   float *gmz = gmX + C * C;     // [3][C]
+  float *gbs = gmz + 3 * C;     // [C][GPB_GLD]  g_Bc[b]
+  float *wd = gbs + C * GPB_GLD;   // [H][C + 1]    V1d[o][c']
+  float *wb = wd + H * (C + 1);    // [H][H]        V1b[o][k]
+  for (int i = threadIdx.x; i < H * H; i += 256) wb[i] = a.V0W[(size_t)(i >> 6) * ld + H + (i & 63)];
+  for (int i = threadIdx.x; i < C * H; i += 256) gbs[(i >> 6) * GPB_GLD + (i & 63)] = a.g_Bc[(size_t)b * C * H + i];
+  for (int i = threadIdx.x; i < H * C; i += 256) wd[(i / C) * (C + 1) + i % C] = a.V0W[(size_t)(i / C) * ld + 2 * H + 1 + i % C];
   const float cnt = fmaxf(a.xsum[b * 4 + 3], 1.f);
   for (int i = threadIdx.x; i < 3 * C; i += 256) mz[i] = a.Z[(size_t)b * 3 * C + i] - a.xsum[b * 4 + i / C] / cnt;
   __syncthreads();
@@ -165,18 +206,18 @@ __global__ __launch_bounds__(256) void graph_pre_bwd_kernel(GraphPreBwdArgs a) {
   // g_HvT[b,c,k] += sum_o g_Bc[b,c,o] V1b[o,k]
   for (int i = i0; i < C * H; i += istep) {
     int c = i >> 6, k = i & 63;
-    const float *gb = a.g_Bc + ((size_t)b * C + c) * H;
+    const float *gb = gbs + c * GPB_GLD;
     float acc = 0.f;
-    if (a.bf16) { for (int o = 0; o < H; ++o) acc += round_bf(gb[o]) * round_bf(a.V0W[(size_t)o * ld + H + k]); }   // V1b^T g_Bc: bf16 operands
-    else { for (int o = 0; o < H; ++o) acc += gb[o] * a.V0W[(size_t)o * ld + H + k]; }
+    if (a.bf16) { for (int o = 0; o < H; ++o) acc += round_bf(gb[o]) * round_bf(wb[o * H + k]); }   // V1b^T g_Bc: bf16 operands
+    else { for (int o = 0; o < H; ++o) acc += gb[o] * wb[o * H + k]; }
     a.g_HvT[((size_t)b * C + c) * H + k] += acc;
   }
   // g_mX[c'][c] = sum_o g_Bc[b,c,o] V1d[o,c']   (every workgroup: all of it)
   for (int i = threadIdx.x; i < C * C; i += 256) {
     int cp = i / C, c = i % C;
-    const float *gb = a.g_Bc + ((size_t)b * C + c) * H;
+    const float *gb = gbs + c * GPB_GLD;
     float acc = 0.f;
-    for (int o = 0; o < H; ++o) acc += gb[o] * a.V0W[(size_t)o * ld + 2 * H + 1 + cp];
+    for (int o = 0; o < H; ++o) acc += gb[o] * wd[o * (C + 1) + cp];
     gmX[cp * C + c] = acc;
   }
   __syncthreads();
@@ -201,7 +242,7 @@ int graph_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *sh
   float *wg_mxt = L->wg_node + 7 * wg_node_rows(L) * H;   // this stage's operand region of wg_node (kernels.h)
   GraphPreBwdArgs a{L->xsum, L->Z, L->g_Bc, L->g_Zp, L->params[FASTEGNN_P_VIRT0_W], L->g_Z, L->g_HvT, L->g_xbar, wg_mxt,
                     L->B, L->C, has(L, FASTEGNN_F_BF16) ? 1 : 0};
-  const size_t lds = (size_t)(6 * L->C + L->C * L->C) * sizeof(float);
+  const size_t lds = graph_pre_bwd_lds_floats(L->C) * sizeof(float);
   { ProfScope _ps_graph_pre_bwd_kernel(K_GRAPH_PRE_BWD, st); hipLaunchKernelGGL(graph_pre_bwd_kernel, dim3(L->B, GPB_SPLIT), dim3(256), lds, st, a); }
   int rc = check_launch("graph_pre_bwd_kernel");
   if (rc) return rc;

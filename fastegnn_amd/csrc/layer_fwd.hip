@@ -114,85 +114,116 @@ int node_pre_forward(const fastegnn_layer_t *L, hipStream_t st) {
 // =====================================================================================
 // S2a graph_xsum: per-graph sum of coordinates and node count (global_mean_pool(coord), :212)
 // =====================================================================================
-// A wave owns XSUM_PER_WAVE consecutive nodes and walks them 64 at a time (lane = node).  (Round 4 measured 256 nodes per wave --
-// four iterations instead of sixteen, four times the waves: 26 us per launch at 100 000 nodes either way; with one big graph the
-// launch is bound by the same-address atomics of its 98 - 391 waves, not by the loop.)  data_batch is ascending, so a
-// 64-node group normally lies inside one graph: the lanes keep partial sums and the wave leaves ONE atomic set per
-// (wave, graph) run; groups that straddle graphs (mini-batches of small graphs) are reduced by a segmented scan over the
-// lanes (data_batch is sorted, so a graph is a run of lanes) and add once per (group, graph).
-#ifndef FE_XSUM_PER_WAVE
-#define FE_XSUM_PER_WAVE 1024
-#endif
-constexpr int XSUM_PER_WAVE = FE_XSUM_PER_WAVE;
-// (round 6: the nodes per wave are a launch argument -- XSUM_PER_WAVE for large inputs; a small input (a 12 500-node shard, the N-body
-//  mini-batches) gets shorter walks on more waves: at 1 024 nodes per wave a shard's launch was 13 waves x 16 dependent iterations = 15 us)
-__global__ __launch_bounds__(256) void graph_xsum_kernel(const float *x, const int32_t *batch, int N, float *xsum, int PER_WAVE) {
-  const int l = lane_id();
-  const int n0 = global_wave_id() * PER_WAVE, n1 = min(N, n0 + PER_WAVE);
-  if (n0 >= n1) return;
-  int cur = -1;
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-  // (ONE atomic instruction per flush: lanes 0..3 add the four components of the graph's row -- four single-lane atomics per wave
-  // made the launch 26 us long at 100 000 nodes in one graph, every wave queueing on the same cache line four times)
-  auto flush = [&]() {
-    float mine = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float v = s[k];
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-      if (l == k) mine = v;
-      s[k] = 0.f;
-    }
-    if (l < 4) atomicAdd(&xsum[cur * 4 + l], mine);
-  };
-  for (int base = n0; base < n1; base += 64) {
-    const int n = base + l;
-    const bool ok = n < n1;
-    const int b = batch[ok ? n : n1 - 1];
-    const int bf = __builtin_amdgcn_readfirstlane(b), bl = batch[min(base + 63, n1 - 1)];
-    float xv[3] = {0.f, 0.f, 0.f};
-    if (ok) { xv[0] = x[(size_t)n * 3]; xv[1] = x[(size_t)n * 3 + 1]; xv[2] = x[(size_t)n * 3 + 2]; }
-    if (bf == bl) {   // (wave-uniform) the whole group lies in graph bf
-      if (bf != cur) {
-        if (cur >= 0) flush();
-        cur = bf;
-      }
-      s[0] += xv[0]; s[1] += xv[1]; s[2] += xv[2]; s[3] += ok ? 1.f : 0.f;
-    } else {
-      if (cur >= 0) flush();
-      cur = -1;
-      // segmented inclusive scan: after it the LAST lane of every run of equal graph ids holds the run's sums
-      const int bb = ok ? b : -1;
-      float v[4] = {xv[0], xv[1], xv[2], ok ? 1.f : 0.f};
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int bu = __shfl_up(bb, off);
-        float u[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) u[k] = __shfl_up(v[k], off);
-        if (l >= off && bu == bb) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) v[k] += u[k];
-        }
-      }
-      const int bn = __shfl_down(bb, 1);
-      if (ok && (l == 63 || bn != bb)) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) atomicAdd(&xsum[b * 4 + k], v[k]);
-      }
-    }
-  }
-  if (cur >= 0) flush();
+// No atomics and no zeroing: the sum of a graph is built in an order that depends on the node range of the graph and on the
+// block size alone, so two runs give the same bits.
+//   1. graph_xsum_part_kernel: the nodes are cut into fixed blocks of NB (xsum_block_nodes); one wave per block adds the block's
+//      coordinates -- lane l takes the nodes l, l + 64, ... of the block in ascending order, then a butterfly over the lanes -- and
+//      stores the block's partial.  A block that straddles graphs has a partial nobody reads.
+//   2. xsum_combine (one 256-thread workgroup per graph): the nodes [lo, hi) of the graph are the items
+//        head nodes [lo, fb NB) | partials of the whole blocks fb .. lb - 1 | tail nodes [lb NB, hi)
+//      (a graph without a whole block: its nodes alone).  Thread t adds the items t, t + 256, ... in ascending order, a butterfly
+//      combines the lanes of a wave, the four waves are added as (w0 + w1) + (w2 + w3).  The count is hi - lo.
+// The combine runs inside graph_pre_fwd_kernel when the layer is run as a whole (fastegnn_layer_forward: one launch fewer, every
+// workgroup of a graph computes the same bits and the first one writes L->xsum) and as graph_xsum_combine_kernel behind the
+// staged entry point: the same function, the same bits.
+// The partials of the layer call live in L->aggm (free until the edge stage writes it).  The staged call has no layer buffer to
+// spare: its partials live in g_xsum_part, ONE array per device, so staged graph_xsum calls on different streams of one device
+// must not overlap.
+constexpr int XS_BLOCK = 256;     // nodes per block while that leaves at most XS_MAXBLK blocks (1 M nodes): 391 waves at 100 000 nodes
+constexpr int XS_MAXBLK = 4096;
+__device__ float g_xsum_part[XS_MAXBLK * 4];
+static int xsum_block_nodes(int N) {
+  const int k = cdiv(N, XS_BLOCK * XS_MAXBLK);
+  return XS_BLOCK * (k < 1 ? 1 : k);
 }
 
+__global__ __launch_bounds__(256) void graph_xsum_part_kernel(const float *x, int N, int NB, float *part) {
+  if (!part) part = g_xsum_part;
+  const int l = lane_id(), blk = global_wave_id();
+  if ((long)blk * NB >= N) return;
+  const int n0 = blk * NB, n1 = min(N, n0 + NB);
+  float s[3] = {0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int n = n0 + l; n < n1; n += 64) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] += x[(size_t)n * 3 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off);
+  if (l == 0) *reinterpret_cast<f32x4 *>(part + (size_t)blk * 4) = f32x4{s[0], s[1], s[2], 0.f};
+}
+
+// first n in [0, N) with batch[n] >= key (N if none): a 256-ary search by the whole workgroup, three rounds at 100 000 nodes
+__device__ __forceinline__ int xsum_lower_bound(const int32_t *batch, int N, int key) {
+  int a = 0, e = N;
+  while (a < e) {
+    const int S = (e - a + 255) / 256, idx = a + (int)threadIdx.x * S;
+    const int c = __syncthreads_count(idx < e && batch[idx] < key);
+    if (c == 0) e = a;
+    else {
+      e = min(e, a + c * S);
+      a += (c - 1) * S + 1;
+    }
+  }
+  return a;
+}
+// out[0..3] = (sum x, sum y, sum z, count) of graph b in every thread of the 256-thread workgroup; red: 16 floats of LDS.
+// The node range comes from gptr (clamped to [0, N]) when the layer carries it, from the ascending batch otherwise.
+__device__ __forceinline__ void xsum_combine(const float *x, const float *part, const int32_t *batch, const int32_t *gptr, int N,
+                                             int NB, int b, float *red, float out[4]) {
+  if (!part) part = g_xsum_part;
+  int lo, hi;
+  if (gptr) {
+    lo = min(max(gptr[b], 0), N);
+    hi = min(max(gptr[b + 1], lo), N);
+  } else {
+    lo = xsum_lower_bound(batch, N, b);
+    hi = xsum_lower_bound(batch, N, b + 1);
+  }
+  int fb = (lo + NB - 1) / NB, lb = hi / NB;
+  if (fb >= lb) fb = lb = hi / NB + 1;                 // no whole block: all nodes are "head" nodes
+  const int nhead = min(hi, fb * NB) - lo, nblk = lb - fb, nitems = hi - lo - nblk * (NB - 1);
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < nitems; i += 256) {
+    const float *p = i < nhead ? x + (size_t)(lo + i) * 3
+                               : (i < nhead + nblk ? part + (size_t)(fb + i - nhead) * 4 : x + (size_t)(lb * NB + i - nhead - nblk) * 3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] += p[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off);
+  const int l = lane_id(), w = threadIdx.x >> 6;
+  if (l < 3) red[w * 4 + l] = s[l];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = (red[k] + red[4 + k]) + (red[8 + k] + red[12 + k]);
+  out[3] = (float)(hi - lo);
+}
+__device__ __forceinline__ float xsum_pick(const float v[4], int k) { return k == 0 ? v[0] : (k == 1 ? v[1] : (k == 2 ? v[2] : v[3])); }
+__global__ __launch_bounds__(256) void graph_xsum_combine_kernel(const float *x, const int32_t *batch, const int32_t *gptr, int N, int NB,
+                                                                 float *xsum) {
+  __shared__ float red[16];
+  float v[4];
+  xsum_combine(x, nullptr, batch, gptr, N, NB, blockIdx.x, red, v);
+  if (threadIdx.x < 4) xsum[blockIdx.x * 4 + threadIdx.x] = xsum_pick(v, threadIdx.x);
+}
+
+// the block partials of L->x into `part` ([cdiv(N, NB)][4] floats; null: g_xsum_part)
+int graph_xsum_partials(const fastegnn_layer_t *L, float *part, hipStream_t st) {
+  FE_REQUIRE(L->x && (L->gptr || L->batch), "graph_xsum: null buffer");
+  if (L->N == 0) return FASTEGNN_OK;
+  const int NB = xsum_block_nodes(L->N);
+  { ProfScope _ps_graph_xsum_kernel(K_XSUM, st); hipLaunchKernelGGL(graph_xsum_part_kernel, dim3(cdiv(cdiv(L->N, NB), 4)), dim3(256), 0, st, L->x, L->N, NB, part); }
+  return check_launch("graph_xsum_part_kernel");
+}
 int graph_xsum(const fastegnn_layer_t *L, hipStream_t st) {
-  FE_REQUIRE(L->xsum && L->batch && L->x, "graph_xsum: null buffer");
-  (void)hipMemsetAsync(L->xsum, 0, (size_t)L->B * 4 * sizeof(float), st);
-  // nodes per wave: ~64 waves in flight for a small input (same-address atomics: one set per wave), XSUM_PER_WAVE at most
-  int per_wave = (cdiv(L->N, 64) + 63) / 64 * 64;
-  per_wave = per_wave < 64 ? 64 : (per_wave > XSUM_PER_WAVE ? XSUM_PER_WAVE : per_wave);
-  if (L->N > 0) { ProfScope _ps_graph_xsum_kernel(K_XSUM, st); hipLaunchKernelGGL(graph_xsum_kernel, dim3(cdiv(L->N, 4 * per_wave)), dim3(256), 0, st, L->x, L->batch, L->N, L->xsum, per_wave); }   // 4 waves x per_wave nodes
-  return check_launch("graph_xsum_kernel");
+  FE_REQUIRE(L->xsum, "graph_xsum: null buffer");
+  int rc = graph_xsum_partials(L, nullptr, st);
+  if (rc || L->B == 0) return rc;
+  { ProfScope _ps_graph_xsum_kernel(K_XSUM, st); hipLaunchKernelGGL(graph_xsum_combine_kernel, dim3(L->B), dim3(256), 0, st, L->x, L->batch, L->gptr, L->N, xsum_block_nodes(L->N), L->xsum); }
+  return check_launch("graph_xsum_combine_kernel");
 }
 
 // =====================================================================================
@@ -203,19 +234,47 @@ struct GraphPreArgs {
   const float *xsum, *Z, *HvT, *V0W, *V0B;
   float *Bc;
   int B, C, bf16;
+  // the layer call (x non-null): xsum is combined here from the block partials and WRITTEN, and the pools of the virtual stage
+  // are zeroed (poolV may be null)
+  const float *x, *part;
+  const int32_t *batch, *gptr;
+  int N, NB;
+  float *xsum_out, *poolV, *poolX;
 };
 // grid (B, GP_SPLIT): the C*64 outputs of a graph are dealt to GP_SPLIT workgroups (each recomputes the graph's small
-// Gram matrix): with one big graph the stage was a single workgroup on one CU
+// Gram matrix): with one big graph the stage was a single workgroup on one CU.
+// The V1b and V1d blocks of edge_mlp_virtual.0.weight (row stride 2H + 1 + C) and the graph's Hv rows are staged in LDS with
+// coalesced loads: a lane owns an output feature, i.e. a ROW of the weight, and read it from global memory one scattered dword per k.
 constexpr int GP_SPLIT = 4;
+constexpr int GP_WLD = H + 1;   // row stride of the V1b tile in LDS: lanes along o hit 64 banks
+static size_t graph_pre_lds_floats(int C) { return (size_t)3 * C + C * C + H * GP_WLD + (size_t)H * (C + 1) + (size_t)C * H + 16; }
 __global__ __launch_bounds__(256) void graph_pre_fwd_kernel(GraphPreArgs a) {
   extern __shared__ float sm[];
   const int C = a.C, b = blockIdx.x, ld = 2 * H + 1 + C;
-  float *mz = sm;           // [3][C]
-  float *mX = sm + 3 * C;   // [C][C]
-  const float cnt = fmaxf(a.xsum[b * 4 + 3], 1.f);
+  float *mz = sm;                 // [3][C]
+  float *mX = mz + 3 * C;         // [C][C]
+  float *wb = mX + C * C;         // [H][GP_WLD]   V1b[o][k]
+  float *wd = wb + H * GP_WLD;    // [H][C + 1]    V1d[o][d]
+  float *hv = wd + H * (C + 1);   // [C][H]
+  float *red = hv + C * H;        // [16]
+  for (int i = threadIdx.x; i < H * H; i += 256) wb[(i >> 6) * GP_WLD + (i & 63)] = a.V0W[(size_t)(i >> 6) * ld + H + (i & 63)];
+  for (int i = threadIdx.x; i < H * C; i += 256) wd[(i / C) * (C + 1) + i % C] = a.V0W[(size_t)(i / C) * ld + 2 * H + 1 + i % C];
+  for (int i = threadIdx.x; i < C * H; i += 256) hv[i] = a.HvT[(size_t)b * C * H + i];
+  float xs[4];
+  if (a.x) {
+    const int gid = (blockIdx.x * gridDim.y + blockIdx.y) * 256 + threadIdx.x, gstep = gridDim.x * gridDim.y * 256;
+    if (a.poolV) for (int i = gid; i < a.B * C * H; i += gstep) a.poolV[i] = 0.f;
+    for (int i = gid; i < a.B * 3 * C; i += gstep) a.poolX[i] = 0.f;
+    xsum_combine(a.x, a.part, a.batch, a.gptr, a.N, a.NB, b, red, xs);
+    if (blockIdx.y == 0 && threadIdx.x < 4) a.xsum_out[b * 4 + threadIdx.x] = xsum_pick(xs, threadIdx.x);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xs[k] = a.xsum[b * 4 + k];
+  }
+  const float cnt = fmaxf(xs[3], 1.f);
   for (int i = threadIdx.x; i < 3 * C; i += 256) {
     int k = i / C;
-    mz[i] = a.Z[(size_t)b * 3 * C + i] - a.xsum[b * 4 + k] / cnt;
+    mz[i] = a.Z[(size_t)b * 3 * C + i] - (k == 0 ? xs[0] : (k == 1 ? xs[1] : xs[2])) / cnt;
   }
   __syncthreads();
   for (int i = threadIdx.x; i < C * C; i += 256) {
@@ -225,20 +284,22 @@ __global__ __launch_bounds__(256) void graph_pre_fwd_kernel(GraphPreArgs a) {
   __syncthreads();
   for (int i = blockIdx.y * 256 + threadIdx.x; i < C * H; i += 256 * gridDim.y) {
     int c = i >> 6, o = i & 63;
-    const float *w = a.V0W + (size_t)o * ld;
-    const float *hv = a.HvT + ((size_t)b * C + c) * H;
+    const float *w = wb + o * GP_WLD, *h = hv + c * H;
     float acc = a.V0B[o];
-    if (a.bf16) { for (int k = 0; k < H; ++k) acc += round_bf(w[H + k]) * round_bf(hv[k]); }   // V1b Hv: bf16 operands
-    else { for (int k = 0; k < H; ++k) acc += w[H + k] * hv[k]; }
-    for (int d = 0; d < C; ++d) acc += w[2 * H + 1 + d] * mX[d * C + c];   // Gram columns: always fp32
+    if (a.bf16) { for (int k = 0; k < H; ++k) acc += round_bf(w[k]) * round_bf(h[k]); }   // V1b Hv: bf16 operands
+    else { for (int k = 0; k < H; ++k) acc += w[k] * h[k]; }
+    for (int d = 0; d < C; ++d) acc += wd[o * (C + 1) + d] * mX[d * C + c];   // Gram columns: always fp32
     a.Bc[((size_t)b * C + c) * H + o] = acc;
   }
 }
-int graph_pre_forward(const fastegnn_layer_t *L, hipStream_t st) {
+// part non-null: the layer call -- xsum from the block partials in `part` (graph_xsum_partials), pools zeroed
+int graph_pre_forward(const fastegnn_layer_t *L, hipStream_t st, float *part) {
   FE_REQUIRE(L->xsum && L->Z && L->HvT && L->Bc, "graph_pre_forward: null buffer");
+  FE_REQUIRE(!part || (L->x && L->poolX && (L->gptr || L->batch)), "graph_pre_forward: null buffer");
   GraphPreArgs a{L->xsum, L->Z, L->HvT, L->params[FASTEGNN_P_VIRT0_W], L->params[FASTEGNN_P_VIRT0_B], L->Bc, L->B, L->C,
-                 has(L, FASTEGNN_F_BF16) ? 1 : 0};
-  const size_t lds = (size_t)(3 * L->C + L->C * L->C) * sizeof(float);
+                 has(L, FASTEGNN_F_BF16) ? 1 : 0, part ? L->x : nullptr, part, L->batch, L->gptr, L->N, xsum_block_nodes(L->N),
+                 L->xsum, L->poolV, L->poolX};
+  const size_t lds = graph_pre_lds_floats(L->C) * sizeof(float);
   { ProfScope _ps_graph_pre_fwd_kernel(K_GRAPH_PRE_FWD, st); hipLaunchKernelGGL(graph_pre_fwd_kernel, dim3(L->B, GP_SPLIT), dim3(256), lds, st, a); }
   return check_launch("graph_pre_fwd_kernel");
 }
@@ -392,7 +453,8 @@ int edge_forward(const fastegnn_layer_t *L, hipStream_t st) {
 #include "virt_fwd.h"   // VIRT_FWD_IMG_FLOATS, virt_fwd_lds_bytes, virt_fwd_kernel<MODE, PAIR>
 namespace fe {
 
-int virt_forward(const fastegnn_layer_t *L, hipStream_t st) {
+// pools_zeroed: poolV / poolX were zeroed on this stream already (the layer call: graph_pre_fwd_kernel)
+int virt_forward(const fastegnn_layer_t *L, hipStream_t st, bool pools_zeroed) {
   const bool egnn = has(L, FASTEGNN_F_EGNN);
   // h_out == NULL && HvT_out == NULL (FastEGNN wiring): the node update of this layer is not wanted -- npre and poolV are not written
   // and may be null as well (include/fastegnn_hip.h)
@@ -404,7 +466,7 @@ int virt_forward(const fastegnn_layer_t *L, hipStream_t st) {
   FE_REQUIRE(egnn ? L->C == 0 : (L->Bc && L->Z && (!node || L->poolV) && L->poolX && L->C >= 1 && L->C <= 64),
              "virt_forward: virtual_channels must be in [1,64] (0 with FASTEGNN_F_EGNN) and the virtual buffers non-null");
   FE_REQUIRE(L->na == 0 || L->node_attr, "virt_forward: node_attr null");
-  if (L->C > 0) {
+  if (L->C > 0 && !pools_zeroed) {
     if (node) (void)hipMemsetAsync(L->poolV, 0, (size_t)L->B * L->C * H * sizeof(float), st);
     (void)hipMemsetAsync(L->poolX, 0, (size_t)L->B * 3 * L->C * sizeof(float), st);
   }
@@ -443,10 +505,12 @@ struct GraphPostArgs {
 };
 __global__ __launch_bounds__(256) void graph_post_fwd_kernel(GraphPostArgs a) {
   const bool bf = a.flags & FASTEGNN_F_BF16;   // bf16 operand mode: activations rounded, images hold rounded weights
-  // (the three images are read straight from global memory: with B*C = 16 rows the stage is ONE tile, and staging 48 KB
-  // through LDS first measured slower -- 14.1 vs 13.3 us per launch)
-  const int l = lane_id(), j = l & 15, q = l >> 4;
-  const int wave = global_wave_id(), nwaves = (gridDim.x * blockDim.x) >> 6;
+  // One workgroup per tile of 16 rows, the 64 output features of each product dealt to its four waves (gemm64_block).  With
+  // B*C = 16 rows the stage is ONE tile: a single wave running the products one after the other, each behind its own fragment
+  // loads from global memory, was the whole launch.  The waves exchange the one vector the next product contracts over (u5)
+  // through LDS.
+  __shared__ __attribute__((aligned(16))) float xt[16 * TS];
+  const int l = lane_id(), j = l & 15, q = l >> 4, w = wave_id();
   const int M = a.B * a.C, ntiles = (M + 15) >> 4;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.B * 3 * a.C; i += gridDim.x * blockDim.x) {
     const int b = i / (3 * a.C);
@@ -456,7 +520,11 @@ __global__ __launch_bounds__(256) void graph_post_fwd_kernel(GraphPostArgs a) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M * H; i += gridDim.x * blockDim.x) a.HvT_out[i] = a.HvT[i];
     return;
   }
-  for (int tile = wave; tile < ntiles; tile += nwaves) {
+  f32x4 f5a[4], f5b[4], f6[4];
+  gemm64_frags(a.wpack + (size_t)I_W5A * IMG, w, f5a);
+  gemm64_frags(a.wpack + (size_t)I_W5B * IMG, w, f5b);
+  gemm64_frags(a.wpack + (size_t)I_W6 * IMG, w, f6);
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int m = tile * 16 + j;
     const bool valid = m < M;
     const int mc = valid ? m : M - 1;
@@ -464,14 +532,17 @@ __global__ __launch_bounds__(256) void graph_post_fwd_kernel(GraphPostArgs a) {
     const float inv = 1.0f / fmaxf(a.xsum[b * 4 + 3], 1.f);
     const Vec hv = vload_row(a.HvT + (size_t)mc * H, q);
     const Vec pm = vscale(vload_row(a.poolV + (size_t)mc * H, q), inv);
-    Vec z5 = vload_vec(a.b5, q);
-    gemm64(a.wpack + (size_t)I_W5A * IMG, bf ? vround(hv) : hv, z5);
-    gemm64(a.wpack + (size_t)I_W5B * IMG, bf ? vround(pm) : pm, z5);
-    Vec out = vload_vec(a.b6, q);
-    const Vec u5 = vsilu(z5 FE_ACT(a));
-    gemm64(a.wpack + (size_t)I_W6 * IMG, bf ? vround(u5) : u5, out);
-    if (a.flags & FASTEGNN_F_RESIDUAL) vadd(out, hv);
-    if (valid) vstore_row(a.HvT_out + (size_t)m * H, q, out);
+    f32x4 z5 = vload_block(a.b5, w, q);
+    gemm64_block(f5a, bf ? vround(hv) : hv, z5);
+    gemm64_block(f5b, bf ? vround(pm) : pm, z5);
+    vstore_block(xt + j * TS, w, q, vblock(z5, [&](const Vec &v) { return vsilu(v FE_ACT(a)); }));
+    __syncthreads();
+    const Vec u5 = vload_row(xt + j * TS, q);
+    f32x4 out = vload_block(a.b6, w, q);
+    gemm64_block(f6, bf ? vround(u5) : u5, out);
+    if (a.flags & FASTEGNN_F_RESIDUAL) out += vload_block(a.HvT + (size_t)mc * H, w, q);
+    if (valid) vstore_block(a.HvT_out + (size_t)m * H, w, q, out);
+    __syncthreads();   // xt is rewritten by the next tile
   }
 }
 // HvT_out == NULL && h_out == NULL: node_model_virtual is not wanted -- the coordinate part alone (the same expression as above)
@@ -496,7 +567,7 @@ int graph_post_forward(const fastegnn_layer_t *L, hipStream_t st) {
              "graph_post_forward: null buffer");
   GraphPostArgs a{L->xsum, L->Z, L->HvT, L->poolV, L->poolX, L->wpack, L->params[FASTEGNN_P_NODEV0_B],
                   L->params[FASTEGNN_P_NODEV2_B], L->Z_out, L->HvT_out, L->B, L->C, L->flags, L->act_param};
-  int grid = cdiv(cdiv((long)L->B * L->C, 16), 4);
+  int grid = cdiv((long)L->B * L->C, 16);   // one workgroup per tile
   if (grid > 256) grid = 256;
   if (grid < 1) grid = 1;
   { ProfScope _ps_graph_post_fwd_kernel(K_GRAPH_POST_FWD, st); hipLaunchKernelGGL(graph_post_fwd_kernel, dim3(grid), dim3(256), 0, st, a); }

@@ -6,6 +6,8 @@
 namespace fe {
 
 // ---------------------------------------------------------------- embedding (FastEGNN.py:271)
+// (one thread per element, one dword store: four features per thread and a 16-byte store measured 29.6 against 19.2 us per step
+// at cfg4 -- profiles/small_launches.txt)
 __global__ void embed_fwd_kernel(const float *nf, int N, int nfd, const float *W, const float *b, float *h) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)N * H) return;
@@ -519,55 +521,93 @@ struct WgsArgs {
 // workgroup -- and at most 256 workgroups (64 measured 0.27 instead of 0.05 ms per step at cfg4: too few rows in flight): the gradient of embedding_in is the end of the whole backward chain, a column sum
 // over N rows that cancels; with fp32 chains and up to 512 float atomics in arrival order it measured 2.4 x the reference's
 // own error on the goldens.  The final += into dW / db is still a float atomic per workgroup: <= 256 well-rounded partials.)
-__global__ __launch_bounds__(256) void wgrad_small_kernel(WgsArgs a) {
-  const int o = threadIdx.x & 63, w = wave_id();
+// G is streamed with 16-byte loads: a lane owns four features of one row, a wave-instruction covers four rows (lane >> 4), and
+// WGS_U of them are in flight per lane (64 KB per workgroup of eight waves) together with the rows' F values -- every lane loads its
+// own row's KF values, the sixteen lanes of a row share the address, so F costs one request per row and nothing waits on it in a
+// chain.  KF is a template argument: the loads of a step are straight-line code and a lane keeps 4 (KF + 1) accumulators, not 36.
+// A lane adds its rows in ascending order; the four row groups of a wave (shuffles), then the eight waves (LDS), are combined in
+// a fixed order: the partial that leaves the workgroup does not depend on the run.
+constexpr int WGS_U = 8, WGS_WAVES = 8;
+template <int KF>
+__global__ __launch_bounds__(64 * WGS_WAVES) void wgrad_small_kernel(WgsArgs a) {
+  constexpr int KA = KF > 0 ? KF : 1;
+  const int l = lane_id(), w = wave_id(), sub = l >> 4, o4 = (l & 15) * 4;
   const long m0 = (long)blockIdx.x * a.rows_per_wg;
   long m1 = m0 + a.rows_per_wg;
   if (m1 > a.M) m1 = a.M;
-  double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double bs = 0.;
-  long m = m0 + w;
-  for (; m + 12 < m1; m += 16) {   // four rows in flight per wave
-    float g[4];
+  double acc[KA][4], bs[4] = {0., 0., 0., 0.};
 #pragma unroll
-    for (int u = 0; u < 4; ++u) g[u] = a.G[(size_t)(m + 4 * u) * a.ldg + o];
+  for (int k = 0; k < KA; ++k)
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      bs += (double)g[u];
+    for (int c = 0; c < 4; ++c) acc[k][c] = 0.;
+  for (long mb = m0 + 4 * w; mb < m1; mb += 4 * WGS_WAVES * WGS_U) {   // (wave-uniform bounds: 32 rows per step of the workgroup)
+    f32x4 g[WGS_U];
+    float f[WGS_U][KA];
 #pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (k < a.kf) acc[k] += (double)g[u] * (double)a.F[(size_t)(m + 4 * u) * a.ldf + k];
+    for (int u = 0; u < WGS_U; ++u) {
+      const long r = mb + 4 * WGS_WAVES * u + sub;
+      const bool ok = r < m1;
+      const size_t rc = (size_t)(ok ? r : m0);   // (a row past the end: a valid address, its G taken as zero)
+      g[u] = *reinterpret_cast<const f32x4 *>(a.G + rc * a.ldg + o4);
+      if (!ok) g[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < KF; ++k) f[u][k] = a.F[rc * a.ldf + k];
     }
-  }
-  for (; m < m1; m += 4) {
-    const float g = a.G[(size_t)m * a.ldg + o];
-    bs += (double)g;
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (k < a.kf) acc[k] += (double)g * (double)a.F[(size_t)m * a.ldf + k];
-  }
-  __shared__ double red[4][9][H];
+    for (int u = 0; u < WGS_U; ++u)
 #pragma unroll
-  for (int k = 0; k < 8; ++k) red[w][k][o] = acc[k];
-  red[w][8][o] = bs;
+      for (int c = 0; c < 4; ++c) {
+        const double gd = (double)g[u][c];
+        bs[c] += gd;
+#pragma unroll
+        for (int k = 0; k < KF; ++k) acc[k][c] += gd * (double)f[u][k];
+      }
+  }
+  __shared__ double red[WGS_WAVES][KA + 1][H];
+  auto rows4 = [&](double v) {   // the wave's four row groups: lanes l, l ^ 16, l ^ 32, l ^ 48
+    v += __shfl_xor(v, 16);
+    return v + __shfl_xor(v, 32);
+  };
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+#pragma unroll
+    for (int k = 0; k < KF; ++k) {
+      const double s = rows4(acc[k][c]);
+      if (sub == 0) red[w][k][o4 + c] = s;
+    }
+    const double s = rows4(bs[c]);
+    if (sub == 0) red[w][KA][o4 + c] = s;
+  }
   __syncthreads();
-  if (w == 0) {   // the four waves' partials in a fixed order
-    for (int k = 0; k < a.kf; ++k)
-      atomicAdd(&a.dW[(size_t)o * a.lddw + a.c0 + k], (float)((red[0][k][o] + red[1][k][o]) + (red[2][k][o] + red[3][k][o])));
-    if (a.db) atomicAdd(&a.db[o], (float)((red[0][8][o] + red[1][8][o]) + (red[2][8][o] + red[3][8][o])));
+  const int o = l;
+  auto waves8 = [&](int k) {   // the eight waves' partials in a fixed order
+    return ((red[0][k][o] + red[1][k][o]) + (red[2][k][o] + red[3][k][o])) + ((red[4][k][o] + red[5][k][o]) + (red[6][k][o] + red[7][k][o]));
+  };
+  if (w == 0) {
+#pragma unroll
+    for (int k = 0; k < KF; ++k) atomicAdd(&a.dW[(size_t)o * a.lddw + a.c0 + k], (float)waves8(k));
+    if (a.db) atomicAdd(&a.db[o], (float)waves8(KA));
   }
+}
+template <int KF>
+static void wgrad_small_launch(const WgsArgs &a, unsigned grid, hipStream_t st) {
+  if constexpr (KF < 8) {
+    if (a.kf > KF) return wgrad_small_launch<KF + 1>(a, grid, st);
+  }
+  hipLaunchKernelGGL(wgrad_small_kernel<KF>, dim3(grid), dim3(64 * WGS_WAVES), 0, st, a);
 }
 static int launch_wgrad_small_b(const float *G, int ldg, const float *F, int ldf, int kf, long M, float *dW, int lddw,
                                 int c0, float *db, hipStream_t st) {
   if (M <= 0 || !dW) return FASTEGNN_OK;
   FE_REQUIRE(kf >= 0 && kf <= 8, "wgrad_small: kf > 8 unsupported");
+  FE_REQUIRE(reinterpret_cast<uintptr_t>(G) % 16 == 0 && ldg % 4 == 0, "wgrad_small: G rows must be 16-byte aligned");
   WgsArgs a{G, F, dW, db, M, ldg, ldf, kf, lddw, c0, 0};
   long nsplit = (M + 255) / 256;
   if (nsplit > 256) nsplit = 256;
   long rows = (M + nsplit - 1) / nsplit;
   a.rows_per_wg = (int)rows;
   nsplit = (M + rows - 1) / rows;
-  { ProfScope _ps_wgrad_small_kernel(K_WGRAD_SMALL, st); hipLaunchKernelGGL(wgrad_small_kernel, dim3((unsigned)nsplit), dim3(256), 0, st, a); }
+  { ProfScope _ps_wgrad_small_kernel(K_WGRAD_SMALL, st); wgrad_small_launch<0>(a, (unsigned)nsplit, st); }
   return check_launch("wgrad_small_kernel");
 }
 int launch_dgrad_small(const float *G, long N, int kf, const float *W, int ldw, int c0, float *g_in, int accumulate,

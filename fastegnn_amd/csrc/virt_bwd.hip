@@ -1717,7 +1717,7 @@ static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, flo
 
 // One form for the three wirings: FastEGNN; FastRF (FASTEGNN_F_RF: no node_model -- B4a passes g_h through, Gv = 0, no
 // node_mlp jobs); the EGNN baseline (FASTEGNN_F_EGNN, C = 0: B4a and the node_mlp jobs only).
-int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared) {
+int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, bool acc_zeroed) {
   const bool egnn = has(L, FASTEGNN_F_EGNN), rf = has(L, FASTEGNN_F_RF);
   // g_h_out == NULL && g_HvT_out == NULL (FastEGNN wiring): no gradient arrives for h / Hv, and the forward of this layer skipped the
   // node update -- npre and g_poolV are not read and may be null as well (include/fastegnn_hip.h)
@@ -1732,7 +1732,7 @@ int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared)
                   : (L->Bc && L->Z && (rf || !node || L->g_poolV) && L->g_poolX && L->g_Bc && L->g_Zp && L->wg_virt && L->C >= 1 && L->C <= 64),
              "virt_backward: virtual buffers null or virtual_channels outside [1,64] (0 with FASTEGNN_F_EGNN)");
   const int N = L->N, C = L->C;
-  if (C > 0) {
+  if (C > 0 && !acc_zeroed) {   // (the layer call: graph_post_bwd_kernel has zeroed them)
     (void)hipMemsetAsync(L->g_Bc, 0, (size_t)L->B * C * H * sizeof(float), st);
     (void)hipMemsetAsync(L->g_Zp, 0, (size_t)L->B * 3 * C * sizeof(float), st);
   }
