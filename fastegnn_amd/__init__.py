@@ -7,5 +7,7 @@ from .model import FastEGNN, SortedGraph  # noqa: F401
 from .egnn import EGNN  # noqa: F401
 from .fastrf import FastRF  # noqa: F401
 from .train import FusedAdam, MMDSampler, evaluate, train_epoch, train_step  # noqa: F401
+from .checkpoint import fit, load_checkpoint, save_checkpoint  # noqa: F401
 
-__all__ = ["FastEGNN", "FastRF", "EGNN", "SortedGraph", "FusedAdam", "MMDSampler", "train_step", "train_epoch", "evaluate"]
+__all__ = ["FastEGNN", "FastRF", "EGNN", "SortedGraph", "FusedAdam", "MMDSampler", "train_step", "train_epoch", "evaluate",
+           "fit", "save_checkpoint", "load_checkpoint"]

@@ -207,6 +207,11 @@ def lib(act: bool = False, wide=None):
                                                    C.POINTER(_vp), C.POINTER(_i32)] + [_vp] * 6 + [_vp] * 7 + [C.POINTER(_i32), _vp])
     # a training step's (loss, mse) into the epoch's three fp64 words: additive
     L.fastegnn_loss_accumulate.argtypes = [_vp, _vp, _i32, _vp, _vp]
+    # the training loss without floating-point atomics (its workspace query and the entry point that takes one): additive
+    L.fastegnn_loss_ordered_ws_doubles.restype = C.c_size_t
+    L.fastegnn_loss_ordered_ws_doubles.argtypes = [_i32, _i32]
+    L.fastegnn_loss_mse_mmd_ordered.argtypes = [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp,
+                                                _vp, C.c_size_t, _vp]
     L.fastegnn_selftest_gemm.argtypes = [_vp, _vp, _vp, _i32, _vp]
     L.fastegnn_selftest_rm.argtypes = [_vp, _vp, _vp, _i32, _i32, _vp]
     L.fastegnn_selftest_jreduce.argtypes = [_vp, _vp, _vp]
@@ -302,6 +307,7 @@ EXPORTED = STAGE_FUNCS + [
     "fastegnn_radius_graph_batch_ws_bytes", "fastegnn_radius_graph_batch_count", "fastegnn_radius_graph_batch_fill",
     "fastegnn_cutoff_batch_tmp_bytes", "fastegnn_cutoff_edges_batch", "fastegnn_collate_plan", "fastegnn_collate_gather",
     "fastegnn_collate_graph", "fastegnn_collate_draw", "fastegnn_collate_gather_uniform", "fastegnn_loss_accumulate",
+    "fastegnn_loss_ordered_ws_doubles", "fastegnn_loss_mse_mmd_ordered",
     "fastegnn_profile_enable", "fastegnn_profile_kernels", "fastegnn_profile_name", "fastegnn_profile_collect",
     "fastegnn_comm_unique_id_bytes", "fastegnn_comm_unique_id", "fastegnn_comm_init", "fastegnn_comm_destroy", "fastegnn_comm_rank",
     "fastegnn_comm_world", "fastegnn_comm_all_reduce", "fastegnn_comm_all_gather", "fastegnn_comm_reduce_scatter",

@@ -220,6 +220,117 @@ __global__ __launch_bounds__(256) void grad_sqnorm_final_kernel(const double *pa
   if (threadIdx.x == 0) *out = s;
 }
 
+// ---- the ORDERED training loss (fastegnn_loss_mse_mmd_ordered): the numbers and gradients of loss_mse_kernel + loss_mmd_kernel with no
+// floating-point atomic; the order of every sum is fixed by (N, B, C, S) and the counts (include/fastegnn_hip.h states the rule).
+// workspace: slot x < G of the MSE workgroup x, slot G + b of graph b (G = loss_ordered_mse_grid(N))
+inline int loss_ordered_mse_grid(long n3) {
+  long grid = cdiv(n3, 256 * 8);
+  return grid > 1024 ? 1024 : (grid < 1 ? 1 : (int)grid);
+}
+// stage 1a: g_loc element-wise as loss_mse_kernel writes it; the squares (exact in fp64) summed per thread in grid-stride order, then
+// block_sum_f64, into the workgroup's own slot
+__global__ __launch_bounds__(256) void loss_mse_ordered_kernel(const float *pred, const float *tgt, long n3, float *g_loc, double *part) {
+  __shared__ double red[4];
+  const float inv = 1.0f / (float)n3;
+  double s = 0.0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n3; i += (long)gridDim.x * 256) {
+    const float d = pred[i] - tgt[i];
+    s += (double)d * (double)d;
+    g_loc[i] = 2.f * d * inv;
+  }
+  s = block_sum_f64(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// stage 1b, one workgroup per graph, V and the Sb sampled rows in LDS.  Every gradient element has ONE owner that adds its terms in
+// ascending index order in registers: thread c < C owns gV[c] (a = 0 .. C-1 of the vv term, both of its roles in pair (c, a) and
+// (a, c); then s = 0 .. Sb-1 of the rv term), thread t owns gR[s] for s = t, t + 256, ... (c = 0 .. C-1).  The pair values are
+// loss_mmd_kernel's fp32 ones; each owner evaluates the pairs it needs, so an rv pair is evaluated twice.  The loss terms (vv by the
+// owner of c, rv by the owner of s) are summed in fp64: per thread in that order, then block_sum_f64, into slot b.
+// g_loc: the rows of one graph's sample are distinct nodes and the graphs' samples are disjoint (the header's contract), so the
+// plain read-add-write below, stream-ordered behind stage 1a, is the only add an address gets.
+__global__ __launch_bounds__(256) void loss_mmd_ordered_kernel(const float *pred, const float *vloc, const int32_t *samp,
+                                                               const int32_t *cnt, int B, int C, int S, float sigma, float weight,
+                                                               float *g_loc, float *g_vloc, double *part) {
+  extern __shared__ float sm[];
+  __shared__ double red[4];
+  float *V = sm;           // [C][3]
+  float *R = sm + 3 * C;   // [S][3]
+  const int b = blockIdx.x, t = threadIdx.x;
+  int Sb = cnt ? cnt[b] : S;
+  Sb = Sb < 0 ? 0 : (Sb > S ? S : Sb);   // as loss_mmd_kernel: the staging below must stay inside the S rows of LDS
+  const float i2s = 1.0f / (2.f * sigma * sigma);
+  for (int i = t; i < 3 * C; i += 256) {
+    const int c = i / 3, k = i % 3;
+    V[i] = vloc[((size_t)b * 3 + k) * C + c];
+  }
+  for (int i = t; i < 3 * Sb; i += 256) {
+    const int s = i / 3, k = i % 3;
+    R[i] = pred[(size_t)samp[(size_t)b * S + s] * 3 + k];
+  }
+  __syncthreads();
+  const float w_vv = weight / ((float)B * C * C), w_rv = -2.f * weight / ((float)B * S * C);
+  double lsum = 0.0;
+  if (t < C) {
+    const float v0 = V[3 * t], v1 = V[3 * t + 1], v2 = V[3 * t + 2];
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    for (int a = 0; a < C; ++a) {
+      const float d0 = v0 - V[3 * a], d1 = v1 - V[3 * a + 1], d2 = v2 - V[3 * a + 2];
+      const float dist = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+      const float kv = __expf(-dist * i2s);
+      lsum += (double)(w_vv * kv);
+      if (dist > 0.f) {   // zero subgradient at coincident points, as loss_mmd_kernel
+        const float f = -w_vv * kv * i2s / dist;
+        g0 += f * d0; g1 += f * d1; g2 += f * d2;   // pair (t, a): this thread's node in front
+        g0 += f * d0; g1 += f * d1; g2 += f * d2;   // pair (a, t): the same value, -f * (V_a - V_t)
+      }
+    }
+    for (int s = 0; s < Sb; ++s) {
+      const float d0 = R[3 * s] - v0, d1 = R[3 * s + 1] - v1, d2 = R[3 * s + 2] - v2;
+      const float dist = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+      if (dist > 0.f) {
+        const float f = -w_rv * __expf(-dist * i2s) * i2s / dist;
+        g0 -= f * d0; g1 -= f * d1; g2 -= f * d2;
+      }
+    }
+    g_vloc[((size_t)b * 3 + 0) * C + t] = g0;
+    g_vloc[((size_t)b * 3 + 1) * C + t] = g1;
+    g_vloc[((size_t)b * 3 + 2) * C + t] = g2;
+  }
+  for (int s = t; s < Sb; s += 256) {
+    const float r0 = R[3 * s], r1 = R[3 * s + 1], r2 = R[3 * s + 2];
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float d0 = r0 - V[3 * c], d1 = r1 - V[3 * c + 1], d2 = r2 - V[3 * c + 2];
+      const float dist = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+      const float kv = __expf(-dist * i2s);
+      lsum += (double)(w_rv * kv);
+      if (dist > 0.f) {
+        const float f = -w_rv * kv * i2s / dist;
+        g0 += f * d0; g1 += f * d1; g2 += f * d2;
+      }
+    }
+    float *g = g_loc + (size_t)samp[(size_t)b * S + s] * 3;
+    g[0] += g0; g[1] += g1; g[2] += g2;
+  }
+  lsum = block_sum_f64(lsum, red);
+  if (t == 0) part[b] = lsum;
+}
+// stage 2, ONE workgroup (grad_sqnorm_final_kernel's scheme, once per term): thread i sums the slots i, i + 256, ... of the MSE
+// workgroups, then of the graphs, each in ascending order, each followed by block_sum_f64
+__global__ __launch_bounds__(256) void loss_ordered_final_kernel(const double *part, int G, int B, long n3, float *loss2) {
+  __shared__ double red_mse[4], red_mmd[4];
+  double s = 0.0, m = 0.0;
+  for (int i = threadIdx.x; i < G; i += 256) s += part[i];
+  for (int i = threadIdx.x; i < B; i += 256) m += part[G + i];
+  s = block_sum_f64(s, red_mse);
+  m = block_sum_f64(m, red_mmd);
+  if (threadIdx.x == 0) {
+    const double mse = s / (double)n3;
+    loss2[0] = (float)(mse + m);
+    loss2[1] = (float)mse;
+  }
+}
+
 // ---- the loss of a forward-only epoch (fastegnn_loss_mse_mmd_eval): MSE and MSE + MMD of one batch, no gradients, added into three
 // fp64 words on the device.  The entry point has no workspace argument, so the two-stage scheme above collapses to its second stage:
 // ONE workgroup of 16 waves takes every sum in a fixed order (thread i owns elements i, i + 1024, ...; xor butterfly within a wave;
@@ -458,6 +569,32 @@ int fastegnn_loss_mse_mmd_eval(const float *loc_pred, const float *loc_t, const 
   hipLaunchKernelGGL(loss_eval_kernel, dim3(1), dim3(EVAL_THREADS), lds, (hipStream_t)stream, loc_pred, loc_t, vloc,
                      mmd ? sample_nodes : nullptr, sample_count, (long)N * 3, B, C, S, sigma, weight, acc);
   return check_launch("loss_eval_kernel");
+}
+
+size_t fastegnn_loss_ordered_ws_doubles(int32_t N, int32_t B) {
+  return (size_t)loss_ordered_mse_grid((long)(N > 0 ? N : 0) * 3) + (size_t)(B > 0 ? B : 0);
+}
+
+int fastegnn_loss_mse_mmd_ordered(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                                  const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
+                                  float weight, float *loss2, float *g_loc, float *g_vloc, double *ws, size_t ws_doubles,
+                                  void *stream) {
+  FE_REQUIRE(N >= 0 && B >= 0 && C >= 0 && S >= 0, "loss_mse_mmd_ordered: negative size");
+  FE_REQUIRE(C <= 256 && S <= 4096, "loss_mse_mmd_ordered: C <= 256 and S <= 4096");
+  FE_REQUIRE(loss2 && ws && (N == 0 || (loc_pred && loc_t && g_loc)), "loss_mse_mmd_ordered: null pointer");
+  FE_REQUIRE(B == 0 || ((C == 0 || (vloc && g_vloc)) && (S == 0 || (sample_nodes && loc_pred && g_loc))),
+             "loss_mse_mmd_ordered: null pointer");
+  FE_REQUIRE(ws_doubles >= fastegnn_loss_ordered_ws_doubles(N, B), "loss_mse_mmd_ordered: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const long n3 = (long)N * 3;
+  const int grid = loss_ordered_mse_grid(n3);
+  hipLaunchKernelGGL(loss_mse_ordered_kernel, dim3(grid), dim3(256), 0, st, loc_pred, loc_t, n3, g_loc, ws);
+  const size_t lds = (size_t)(3 * C + 3 * S) * sizeof(float);
+  if (B > 0)   // no graph: the MSE only
+    hipLaunchKernelGGL(loss_mmd_ordered_kernel, dim3(B), dim3(256), lds, st, loc_pred, vloc, sample_nodes, sample_count, B, C, S,
+                       sigma, weight, g_loc, g_vloc, ws + grid);
+  hipLaunchKernelGGL(loss_ordered_final_kernel, dim3(1), dim3(256), 0, st, (const double *)ws, grid, B, n3, loss2);
+  return check_launch("loss_mse_mmd_ordered");
 }
 
 int fastegnn_loss_accumulate(const float *loss, const float *mse, int32_t B, double *acc, void *stream) {

@@ -357,6 +357,27 @@ class DataLoader:
             b = collate([self.dataset[j] for j in order[i * self.batch_size:(i + 1) * self.batch_size]])
             yield b.to(self.device) if self.device is not None else b
 
+    def state_dict(self) -> dict:
+        return _generator_state(self.generator)
+
+    def load_state_dict(self, state) -> None:
+        _load_generator_state(self.generator, state, "DataLoader")
+
+
+def _generator_state(generator) -> dict:
+    """what a loader keeps between epochs: the state of its OWN ``torch.Generator`` (a uint8 tensor), from which the next epoch's
+    ``torch.randperm`` is drawn.  A loader without one draws from torch's global generator, which a checkpoint holds by itself."""
+    return {"generator": None if generator is None else generator.get_state().clone()}
+
+
+def _load_generator_state(generator, state, who) -> None:
+    saved = state.get("generator")
+    if (saved is None) != (generator is None):
+        raise ValueError(f"fastegnn_amd.{who}.load_state_dict: the state was saved {'without' if saved is None else 'with'} a generator "
+                         f"of the loader's own, this loader has {'none' if generator is None else 'one'}")
+    if saved is not None:
+        generator.set_state(saved.cpu().to(torch.uint8))
+
 
 # ---- device-resident packed datasets: a batch is two launches, whatever B is (csrc/collate.hip) ----
 _PACK_KEYS = _NODE_KEYS + ("edge_attr", "loc_mean", "edge_index")   # FASTEGNN_COLLATE_* order (include/fastegnn_hip.h)
@@ -689,6 +710,12 @@ class PackedLoader:
         for i in range(len(self)):
             a, b = i * self.batch_size, min((i + 1) * self.batch_size, n)
             yield self.packed._assemble(ids_dev[a:b], order_host[a:b], self.graphs)
+
+    def state_dict(self) -> dict:
+        return _generator_state(self.generator)
+
+    def load_state_dict(self, state) -> None:
+        _load_generator_state(self.generator, state, "PackedLoader")
 
 
 def _u64(v) -> int:

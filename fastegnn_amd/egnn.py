@@ -14,8 +14,8 @@ import torch
 from torch import nn
 
 from . import _lib as K
-from .model import (STAGE_SET, RangeGuard, SortedGraph, _PadParams, _PtrTable, _activation_kind, _carve, _fill, _new_layer, _no_backward,
-                    _stream, inference_plan)
+from .model import (STAGE_SET, RangeGuard, SortedGraph, _PadParams, _PtrTable, _activation_kind, _carve, _copyable_state, _fill, _new_layer,
+                    _no_backward, _stream, inference_plan)
 
 H = K.H
 
@@ -238,6 +238,9 @@ class EGNN(nn.Module):
         self._range = RangeGuard()   # automatic wide-range fallback (fastegnn_amd.model.RangeGuard)
         self.deterministic = bool(K.deterministic_default())   # see fastegnn_amd.FastEGNN.deterministic (set before the first call)
         self.to(device)
+
+    def __getstate__(self):
+        return _copyable_state(self)
 
     def _build_spec(self):
         pidx = dict(self.named_parameters())

@@ -120,6 +120,35 @@ class RangeGuard:
         except Exception:
             pass
 
+    # ---- copies and checkpoints: the host-mapped words belong to ONE guard (they are freed with it, and a ctypes pointer can be neither
+    # copied nor pickled), so a copy starts without words and allocates its own on first use; the build in use, the mode and the
+    # warnings already given travel with it
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_words"] = None
+        state["launched"] = False
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._words = None
+
+    def __deepcopy__(self, memo):
+        new = type(self).__new__(type(self))
+        new.__setstate__(self.__getstate__())
+        memo[id(self)] = new
+        return new
+
+    def state_dict(self) -> dict:
+        """what a checkpoint keeps of the guard: the build in use"""
+        return {"wide": bool(self.wide)}
+
+    def load_state_dict(self, state) -> None:
+        """a run that had moved to the wide-range build resumes on it, without a warning (a pinned f16x2 build, FASTEGNN_WIDE_RANGE=0 or
+        the FASTEGNN_SAFE_WAITS=1 diagnostic, stays pinned; a guard that is on the wide-range build already stays there)"""
+        if bool(state.get("wide", False)) and self.forced is not False and not K.SAFE_WAITS:
+            self.wide = True
+
     def launch(self, lib, outs, ins=()):
         """queue the check of up to two fp32 output tensors (word OUT) and up to two input tensors (word IN) on the current stream"""
         if self.mode == "off":
@@ -338,6 +367,22 @@ def _check_indices(edge_index, data_batch, N, B):
 
 def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _copyable_state(module) -> dict:
+    """``__getstate__`` of FastEGNN / FastRF / EGNN (``copy.deepcopy``, ``torch.save`` of the module): the module's ``__dict__`` without
+    what is derived from it and rebuilt on the next call -- the specs and the parameter list they index, the graph cache (keyed by
+    addresses of the caller's tensors), the wide path's workspace and its cached constants.  The RangeGuard copies itself (without
+    its host-mapped words)."""
+    state = dict(module.__dict__)
+    for name in ("_spec", "_spec_det", "_plist"):
+        if name in state:
+            state[name] = None
+    if "_graph_cache" in state:
+        state["_graph_cache"] = {}
+    for name in ("_wide_ordered", "_gravity_dev"):
+        state.pop(name, None)
+    return state
 
 
 class _PtrTable:
@@ -892,6 +937,9 @@ class FastEGNN(nn.Module):
     @property
     def _param_index(self):
         return dict(self.named_parameters())
+
+    def __getstate__(self):
+        return _copyable_state(self)
 
     @property
     def deterministic(self) -> bool:

@@ -16,6 +16,11 @@ from . import _lib as K
 from .model import _stream
 
 
+def _capturing() -> bool:
+    """is the current stream being captured into a HIP graph?  (False where there is no GPU: host-side state can always be written)"""
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
 def augment_edge_attr(edge_attr: Optional[torch.Tensor], loc_0: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
     """``cat([edge_attr, ||loc_0[row]-loc_0[col]||], 1)`` (utils/train.py:41-43)."""
     E = edge_index.size(1)
@@ -30,20 +35,26 @@ def augment_edge_attr(edge_attr: Optional[torch.Tensor], loc_0: torch.Tensor, ed
 
 class _MseMmd(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count=None):
+    def forward(ctx, loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count=None, ordered=False):
         dev = loc_pred.device
         loc_pred, vloc, loc_t = loc_pred.contiguous().float(), vloc.contiguous().float(), loc_t.contiguous().float()
         N, (B, _, Cn), S = loc_pred.size(0), vloc.shape, sample_nodes.size(1)
         loss2 = torch.empty(2, dtype=torch.float32, device=dev)
         g_loc, g_vloc = torch.empty_like(loc_pred), torch.empty_like(vloc)
         samp = sample_nodes.to(torch.int32).contiguous()          # no copy when it is int32 and contiguous already
-        if sample_count is None:
+        if sample_count is not None and sample_count.numel() != B:
+            raise ValueError(f"fastegnn_amd.mse_mmd_loss: sample_count has {sample_count.numel()} entries for {B} graphs")
+        if ordered:   # no floating-point atomics: the sums in a fixed order, over a workspace of workgroup partials
+            cnt = sample_count.to(torch.int32).contiguous() if sample_count is not None else None
+            ws = torch.empty(int(K.lib().fastegnn_loss_ordered_ws_doubles(N, B)), dtype=torch.float64, device=dev)
+            K.check(K.lib().fastegnn_loss_mse_mmd_ordered(K.ptr(loc_pred), K.ptr(loc_t), K.ptr(vloc), K.ptr(samp), K.ptr(cnt), N, B, Cn, S,
+                                                          float(sigma), float(weight), K.ptr(loss2), K.ptr(g_loc), K.ptr(g_vloc),
+                                                          K.ptr(ws), ws.numel(), _stream(dev)), "fastegnn_loss_mse_mmd_ordered")
+        elif sample_count is None:
             K.check(K.lib().fastegnn_loss_mse_mmd(K.ptr(loc_pred), K.ptr(loc_t), K.ptr(vloc), K.ptr(samp), N, B, Cn, S,
                                                   float(sigma), float(weight), K.ptr(loss2), K.ptr(g_loc), K.ptr(g_vloc),
                                                   _stream(dev)), "fastegnn_loss_mse_mmd")
         else:
-            if sample_count.numel() != B:
-                raise ValueError(f"fastegnn_amd.mse_mmd_loss: sample_count has {sample_count.numel()} entries for {B} graphs")
             cnt = sample_count.to(torch.int32).contiguous()
             K.check(K.lib().fastegnn_loss_mse_mmd_ragged(K.ptr(loc_pred), K.ptr(loc_t), K.ptr(vloc), K.ptr(samp), K.ptr(cnt),
                                                          N, B, Cn, S, float(sigma), float(weight), K.ptr(loss2), K.ptr(g_loc),
@@ -55,16 +66,19 @@ class _MseMmd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g2):
         g_loc, g_vloc = ctx.saved_tensors
-        return g * g_loc, g * g_vloc, None, None, None, None, None
+        return g * g_loc, g * g_vloc, None, None, None, None, None, None
 
 
-def mse_mmd_loss(loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count=None):
+def mse_mmd_loss(loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count=None, ordered=False):
     """-> (loss, mse): ``MSE(loc_pred, loc_t) + weight * (l_vv - l_rv)`` and the plain MSE the harness logs
     (utils/train.py:104-107,163-165).  ``sample_nodes`` [B,S]: absolute indices of the sampled real nodes.
     ``sample_count`` int32 [B] (``MMDSampler.draw``'s second result): row b holds that many valid entries and the rest is never read
     -- a graph smaller than the sample contributes all its nodes while l_rv keeps the divisor ``B * S * C``, as the reference's
-    variable-size branch does (utils/train.py:121-142).  ``None``: every row is full."""
-    loss, loss2 = _MseMmd.apply(loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count)
+    variable-size branch does (utils/train.py:121-142).  ``None``: every row is full.
+    ``ordered=True``: the same numbers from fastegnn_loss_mse_mmd_ordered -- no floating-point atomics, every sum in an order fixed by
+    the shapes and the counts, so two calls on the same inputs give the same bits (what ``deterministic = True`` promises for the rest of
+    the step).  It relies on the entries of a row being distinct nodes (``MMDSampler``, ``torch.randperm``)."""
+    loss, loss2 = _MseMmd.apply(loc_pred, vloc, loc_t, sample_nodes, sigma, weight, sample_count, bool(ordered))
     return loss, loss2[1]
 
 
@@ -324,6 +338,80 @@ class FusedAdam:
         for p in self.params:
             p.grad = None
 
+    # ---- checkpoints: torch.optim.Adam's state_dict layout, so that either optimizer loads the other's ----
+    def state_dict(self) -> dict:
+        """``{"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [{lr, betas, eps, weight_decay, ..., "params": [0..n-1]}]}``
+        as ``torch.optim.Adam.state_dict()`` lays it out (``step`` a float32 scalar tensor on the host, as torch keeps it), with
+        ``max_grad_norm``, ``capturable`` and ``step_count`` added to the group: ``torch.optim.Adam(params).load_state_dict(...)`` takes it.
+        Every parameter has an entry (a parameter that never had a gradient: step 0, zero moments).  The moments are copies.  In
+        capturable mode the step counts are read from the device: ONE synchronisation, refused inside a stream capture."""
+        if self.capturable and self._dev is not None and _capturing():
+            raise RuntimeError("fastegnn_amd.FusedAdam: state_dict() reads the step counts back from the device, which a stream capture "
+                               "cannot do; save between replays")
+        steps = self.steps
+        state = {i: {"step": torch.tensor(float(steps[i]), dtype=torch.float32),
+                     "exp_avg": self.exp_avg[i].detach().clone(), "exp_avg_sq": self.exp_avg_sq[i].detach().clone()}
+                 for i in range(len(self.params))}
+        group = dict(lr=float(self._lr), betas=(float(self.betas[0]), float(self.betas[1])), eps=float(self.eps),
+                     weight_decay=float(self.weight_decay), amsgrad=False, maximize=False, foreach=None, capturable=self.capturable,
+                     differentiable=False, fused=None, decoupled_weight_decay=False, max_grad_norm=self.max_grad_norm,
+                     step_count=int(self.step_count), params=list(range(len(self.params))))
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict) -> None:
+        """The inverse, also of ``torch.optim.Adam.state_dict()`` over the same parameter list.  A parameter without a state entry gets
+        zero state.  Everything is checked first -- one parameter group, the parameter count, every shape: a mismatch is a ``ValueError``
+        that names the index and leaves the optimizer as it was -- and then written IN PLACE: ``copy_`` into the existing moment tensors
+        and into the existing device buffers of the step counts and the hyper-parameters, so that the pointer tables, and a HIP graph
+        that captured ``step()``, stay valid and continue from the loaded state.  ``capturable`` stays what this optimizer was built
+        with (a checkpoint of either mode loads into either); ``max_grad_norm`` follows the checkpoint when it names one.  Never inside
+        a stream capture."""
+        if _capturing():
+            raise RuntimeError("fastegnn_amd.FusedAdam: load_state_dict() writes the optimizer state between replays, not inside a "
+                               "stream capture")
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise ValueError(f"fastegnn_amd.FusedAdam.load_state_dict: {len(groups)} parameter groups; this optimizer has one")
+        group, n = groups[0], len(self.params)
+        ids = list(group["params"])
+        if len(ids) != n:
+            raise ValueError(f"fastegnn_amd.FusedAdam.load_state_dict: the state holds {len(ids)} parameters, the optimizer {n}")
+        saved = state_dict.get("state", {})
+        unknown = [k for k in saved if k not in ids]
+        if unknown:
+            raise ValueError(f"fastegnn_amd.FusedAdam.load_state_dict: state entries {unknown} name no parameter of the group")
+        entries, steps = [], []
+        for i, (pid, p) in enumerate(zip(ids, self.params)):
+            e = saved.get(pid)
+            if e is not None:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    if tuple(e[key].shape) != tuple(p.shape):
+                        raise ValueError(f"fastegnn_amd.FusedAdam.load_state_dict: {key} of parameter {i} has shape "
+                                         f"{list(e[key].shape)}, the parameter {list(p.shape)}")
+                step = float(e["step"])
+                if step < 0 or step != int(step):
+                    raise ValueError(f"fastegnn_amd.FusedAdam.load_state_dict: step of parameter {i} is {step}")
+            entries.append(e)
+            steps.append(int(float(e["step"])) if e is not None else 0)
+        max_grad_norm = group.get("max_grad_norm", self.max_grad_norm)
+        if max_grad_norm is not None and not self.capturable:
+            raise ValueError("fastegnn_amd.FusedAdam.load_state_dict: the state clips at max_grad_norm, which needs capturable=True")
+        with torch.no_grad():
+            for i, e in enumerate(entries):
+                if e is None:
+                    self.exp_avg[i].zero_(); self.exp_avg_sq[i].zero_()
+                else:
+                    self.exp_avg[i].copy_(e["exp_avg"]); self.exp_avg_sq[i].copy_(e["exp_avg_sq"])
+        self._steps[:] = steps
+        self._lr = float(group["lr"])
+        self.betas = (float(group["betas"][0]), float(group["betas"][1]))
+        self.eps, self.weight_decay = float(group["eps"]), float(group["weight_decay"])
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.step_count = int(group.get("step_count", max(steps, default=0)))
+        if self._dev is not None:
+            self._dev["steps"].copy_(torch.tensor(steps, dtype=torch.int32).reshape(n))
+            self._write_hyper()
+
     def step(self):
         self.step_count += 1
         n = len(self.params)
@@ -372,6 +460,15 @@ def _graph_or_edges(data):
     return graph if graph is not None else data["edge_index"]
 
 
+def _ordered_mode(model) -> bool:
+    """is the model's ordered mode on?  ``model.deterministic`` on the fused modules, ``wide._ordered_of(model)`` on the wide path: the
+    loss then takes its ordered form as well, so that the whole step is free of floating-point atomics where the model is"""
+    if getattr(model, "_wide", False):
+        from . import wide
+        return wide._ordered_of(model) is not None
+    return bool(getattr(model, "deterministic", False))
+
+
 def _forward_backward(model, optimizer, data: dict, sample_nodes, sigma, weight, sample_count=None):
     """augment + forward + MSE/MMD + backward of one iteration (everything of train_step in front of the optimizer)"""
     edge_attr = augment_edge_attr(data.get("edge_attr"), data["loc_0"], data["edge_index"])
@@ -379,7 +476,7 @@ def _forward_backward(model, optimizer, data: dict, sample_nodes, sigma, weight,
     loc_pred, vloc = model(node_loc=data["loc_0"], node_vel=data["vel_0"], node_attr=None,
                            node_feat=data["node_feat"], edge_index=_graph_or_edges(data), loc_mean=data["loc_mean"],
                            data_batch=data["batch"], edge_attr=edge_attr)
-    loss, mse = mse_mmd_loss(loc_pred, vloc, data["loc_t"], sample_nodes, sigma, weight, sample_count)
+    loss, mse = mse_mmd_loss(loc_pred, vloc, data["loc_t"], sample_nodes, sigma, weight, sample_count, ordered=_ordered_mode(model))
     loss.backward()
     return loss.detach(), mse
 

@@ -514,6 +514,35 @@ int fastegnn_loss_mse_mmd_eval(const float *loc_pred, const float *loc_t, const 
  * so that an epoch's graph-weighted means cost ONE read-back after its last step.  Reads nothing back, synchronises nothing,
  * capturable.  B == 0 launches nothing.  FASTEGNN_E_INVALID before any launch for: a null pointer, B < 0. */
 int fastegnn_loss_accumulate(const float *loss, const float *mse, int32_t B, double *acc, void *stream);
+/* The ORDERED training loss: fastegnn_loss_mse_mmd / _ragged (sample_count null: every row full) with NO floating-point atomic.
+ * ADDITIVE exports, found by symbol: FASTEGNN_ABI_VERSION stays 108.  Same outputs (loss2[0..1], g_loc [N,3], g_vloc [B,3,C]), same
+ * ceilings (C <= 256, S <= 4096), same reading of a count outside [0, S] as 0 or S, same zero subgradient at coincident points,
+ * same divisor B * S * C of l_rv whatever the counts; the pair values exp(-d / 2 sigma^2) and the gradient terms are the fp32 ones
+ * of the atomic kernels, the two loss sums are taken in fp64 and rounded once.
+ *   ws  DEVICE double[ws_doubles], ws_doubles >= fastegnn_loss_ordered_ws_doubles(N, B) = G + B with G = clamp(ceil(3 N / 2048), 1,
+ *       1024): written and read by this call only (the caller allocates it; nothing is allocated here).
+ * ORDERING RULE -- the order of every sum is a function of (N, B, C, S) and the counts, never of arrival:
+ *   MSE     workgroup x < G of 256 threads: thread t adds the squares (exact in fp64) of the elements x * 256 + t, + G * 256, ...
+ *           in ascending order; the workgroup sum W is the xor butterfly (offsets 32, 16, .., 1) within each wave, then
+ *           ((w0 + w1) + (w2 + w3)); it goes to ws[x].  g_loc is element-wise.
+ *   MMD     one workgroup per graph b.  gV[c] is owned by thread c: a = 0 .. C-1 of the vv term (the two roles of c in the pairs
+ *           (c, a) and (a, c), one after the other), then s = 0 .. count_b - 1 of the rv term.  gR[s] is owned by thread s mod 256,
+ *           which takes its rows in ascending s and walks c = 0 .. C-1.  Loss terms: the owner of c adds its C vv terms, the owner
+ *           of s its C rv terms, in that order, in fp64; then W as above into ws[G + b].
+ *   final   ONE workgroup: thread t adds ws[t], ws[t + 256], ... below G, then W; the same over the B graph slots; loss2 is written
+ *           once (no memset, no accumulation into it).
+ *   g_loc at the sampled nodes: ONE plain add per address, stream-ordered behind the MSE write.  CONTRACT: the valid entries of a
+ *           row of sample_nodes are distinct and the rows of different graphs name disjoint nodes (torch.randperm(n)[:S] per graph
+ *           in the reference, fastegnn_mmd_sample here).  A repeated node loses all but one of its terms (no fault, not the
+ *           atomic kernels' sum).
+ * Two calls on the same inputs give bit-identical loss2, g_loc and g_vloc.  Capturable, no read-back, no synchronisation.
+ * B == 0 writes the MSE and g_loc only.  FASTEGNN_E_INVALID before any launch for: N < 0, B < 0, C < 0, S < 0, C > 256, S > 4096,
+ * null loss2 / ws, a null tensor that would be read or written, ws_doubles too small. */
+size_t fastegnn_loss_ordered_ws_doubles(int32_t N, int32_t B);
+int fastegnn_loss_mse_mmd_ordered(const float *loc_pred, const float *loc_t, const float *vloc, const int32_t *sample_nodes,
+                                  const int32_t *sample_count, int32_t N, int32_t B, int32_t C, int32_t S, float sigma,
+                                  float weight, float *loss2, float *g_loc, float *g_vloc, double *ws, size_t ws_doubles,
+                                  void *stream);
 
 /* ---- graph construction on device (datasets/simulation/dataset.py:80,96-101) ----
  * radius graph without self loops: all ordered pairs (i, j != i) with |x_i - x_j|^2 <= r^2 (fp32, each
