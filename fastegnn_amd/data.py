@@ -19,6 +19,9 @@
   (``PackedDataset.build_graphs``): the model then sorts nothing per batch.
 * ``PackedStream`` -- a packed dataset of EQUAL-SIZED frames (the N-body sets) streamed through buffers allocated once: the order
   is drawn on the device and ``next()`` is two or three launches with no host work at all, the same every time (capturable).
+* ``TrajectoryDataset`` / ``TrajectoryLoader`` -- trajectories (Water-3D, the protein run) kept on the device as POSITIONS: a sample is
+  (trajectory, start frame), a batch's node tensors are three launches (csrc/traj.hip) and its graphs are built per batch by the
+  batched calls of ``water3d_batch``.  Some thirty times fewer device bytes per sample than the stored graphs of a packed dataset.
 
 All processing is vectorised over the systems of a file and runs on the device the caller names.
 """
@@ -815,3 +818,269 @@ class PackedStream:
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("fastegnn_amd.PackedStream: the state is written between replays, not inside a stream capture")
         self._state[:3].copy_(torch.tensor([_i64(state["seed"]), _i64(state["epoch"]), _i64(state["cursor"])], dtype=torch.int64))
+
+
+# ---- device-resident trajectories: only positions and kinds are stored, a batch's graphs are built per batch (csrc/traj.hip) ----
+_BATCH_KEYS = _NODE_KEYS + ("edge_attr", "edge_index", "loc_mean", "batch", "ptr")   # collate's keys in collate's order
+_TRAJ_SLOT_WORDS = 4   # FASTEGNN_TRAJ_SLOT_WORDS (include/fastegnn_hip.h)
+_NO_CPU_TRAJ = "fastegnn_amd: TrajectoryDataset.batch needs device-resident tables (there is no CPU fallback)"
+
+
+def _upload_ids(ids: torch.Tensor, device) -> torch.Tensor:
+    """host int64 ids -> device without a synchronisation (``PackedDataset._upload``'s way: a fresh pinned buffer, a non-blocking copy)"""
+    if device.type != "cuda":
+        return ids.to(device)
+    staging = torch.empty(ids.shape, dtype=torch.int64, pin_memory=True)
+    staging.copy_(ids)
+    return staging.to(device, non_blocking=True)
+
+
+class HipTrajOps:
+    """The device calls of a trajectory batch on libfastegnn_hip.so (the product path): ``plan``, ``gather`` and ``mean`` are the three
+    launches of its node side (include/fastegnn_hip.h, fastegnn_traj_*), ``edges`` the two batched graph calls ``water3d_batch`` makes.
+    tests/trajectory_ref.py restates the first three in torch, so that tests/test_trajectory_cpu.py can drive the orchestration
+    without a GPU (the ``HipCollateOps`` precedent)."""
+
+    @staticmethod
+    def plan(ids, samples, traj_row0, traj_n, traj_T, traj_kind0, delta_t, ptr_out, slots_out) -> None:
+        """ptr_out [B+1] <- exclusive prefix sums of the node counts of the samples ``ids``; slots_out [B,4] <- per slot the first
+        row in ``pos`` of frames f, f+1, f+delta_t and the first row in ``kind``"""
+        if not ids.is_cuda:
+            raise RuntimeError(_NO_CPU_TRAJ)
+        from . import _lib as K
+        from .model import _stream
+        K.check(K.lib().fastegnn_traj_plan(K.ptr(ids), ids.numel(), K.ptr(samples), samples.size(0), K.ptr(traj_row0), K.ptr(traj_n),
+                                           K.ptr(traj_T), K.ptr(traj_kind0), traj_n.numel(), int(delta_t), K.ptr(ptr_out),
+                                           K.ptr(slots_out), _stream(ids.device)), "fastegnn_traj_plan")
+
+    @staticmethod
+    def gather(ptr, slots, n_nodes, pos, kind, kind_scaled, loc_0, loc_t, vel_0, node_feat, node_attr, batch_out) -> None:
+        """the six node-level tensors of the batch in one launch over its ``n_nodes`` nodes"""
+        if not ptr.is_cuda:
+            raise RuntimeError(_NO_CPU_TRAJ)
+        from . import _lib as K
+        from .model import _stream
+        K.check(K.lib().fastegnn_traj_gather(K.ptr(ptr), K.ptr(slots), ptr.numel() - 1, int(n_nodes), K.ptr(pos), pos.size(0),
+                                             K.ptr(kind), K.ptr(kind_scaled), kind.size(0), K.ptr(loc_0), K.ptr(loc_t), K.ptr(vel_0),
+                                             K.ptr(node_feat), K.ptr(node_attr), K.ptr(batch_out), _stream(ptr.device)),
+                "fastegnn_traj_gather")
+
+    @staticmethod
+    def mean(ptr, slots, pos, loc_mean) -> None:
+        """loc_mean [B,3,C] <- per slot the fp64 mean of its frame-f rows of ``pos``, rounded once, repeated C times"""
+        if not ptr.is_cuda:
+            raise RuntimeError(_NO_CPU_TRAJ)
+        from . import _lib as K
+        from .model import _stream
+        K.check(K.lib().fastegnn_traj_mean(K.ptr(ptr), K.ptr(slots), ptr.numel() - 1, K.ptr(pos), pos.size(0), loc_mean.size(2),
+                                           K.ptr(loc_mean), _stream(ptr.device)), "fastegnn_traj_mean")
+
+    @staticmethod
+    def edges(loc_0, ptr, ptr_host, radius, cutoff_rate):
+        """(edge_index with global ids, dist) of the clouds ``loc_0[ptr[b]:ptr[b+1]]``: the two calls of ``_water3d_batch_edges``, in
+        its order.  ``ptr`` is the device tensor the plan wrote and ``ptr_host`` the same offsets from the host's node counts: the
+        device copy is handed on, so nothing is uploaded, and the calls cost their one read-back (the edge counts)."""
+        from .graphs import _radius_graph_batch, cutoff_edges_batch
+        ei, dist, edge_ptr, edge_ptr_host = _radius_graph_batch(loc_0, ptr, radius)
+        ei, dist, _ = cutoff_edges_batch(ei, dist, edge_ptr, cutoff_rate, edge_ptr_host=edge_ptr_host)
+        return ei, dist
+
+
+_TRAJ_OPS = HipTrajOps
+
+
+def _as_host_tensor(a) -> torch.Tensor:
+    return a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+
+
+class TrajectoryDataset:
+    """Trajectories -- a fixed set of particles observed over T frames -- kept on ``device`` as what they are: ONE fp32 table ``pos``
+    [rows,3] with every trajectory frame after frame, the particle kinds ``kind`` [sum n,1] and ``kind_scaled`` = ``kind / kind.max()``
+    per trajectory, and per trajectory ``row0`` (its first row in ``pos``), ``n``, ``T`` and ``kind0`` (its first row in ``kind``) as
+    int64 device tensors and as host arrays (``row0_host`` ...).  Every offset is 64-bit.  A sample is a pair (trajectory, start frame
+    f) and stands for the graph of ``get_graph_step`` (``datasets/simulation/dataset.py:71-93``; ``datasets/protein/dataset.py:81-173``
+    is the same recipe): ``loc_0 = pos[f]``, ``vel_0 = pos[f+1] - pos[f]``, ``loc_t = pos[f+delta_t]``, the radius graph of ``loc_0``
+    reduced to its shortest ``1 - cutoff_rate`` fraction, edge length as edge attribute, node features ``[|vel|, kind / max kind]``.
+    Nothing of that is stored: 12 bytes per particle and frame, against 48 per node plus 20 per edge and sample of a ``PackedDataset``.
+
+    ``trajectories``: any iterable of ``(key, position [T,n,3], kind [n] or [n,1])`` -- what ``read_trajectories`` yields -- of numpy
+    arrays or tensors; they may differ in n and T.  ``samples``: ``"all"`` (every start frame f with ``f + max(1, delta_t) <= T - 1``,
+    trajectory by trajectory) or an integer array [S,2] of (trajectory index, start frame), validated here: the first pair outside
+    raises ValueError.  ``len(ds)`` = S, ``ds.samples`` the host array, ``ds.frames`` the list of (trajectory key, start frame).
+
+    ``ds[i]`` is the ``Frame`` that ``water3d_frame`` makes of the sample's slices (so ``collate`` and ``DataLoader`` work on the
+    dataset).  ``ds.batch(ids)`` is the ``Batch`` of the samples ``ids``, with ``collate``'s keys in ``collate``'s order: the node
+    tensors by three launches whatever the batch size (csrc/traj.hip), the graphs by the two batched calls of ``water3d_batch``,
+    whose one read-back is the batch's only one.  ``vel_0`` and the copies are bit-equal to the per-sample path; ``node_feat[:,0]`` is
+    ``sqrt((vx*vx + vy*vy) + vz*vz)`` with every operation rounded by itself, and ``loc_mean`` an fp64 sum in a fixed order rounded
+    once (include/fastegnn_hip.h) -- within a unit in the last place of torch's reductions, not bit-equal to them."""
+
+    def __init__(self, trajectories, virtual_channels, delta_t, radius, cutoff_rate=0.0, samples="all", device="cuda"):
+        self.virtual_channels, self.delta_t = int(virtual_channels), int(delta_t)
+        self.radius, self.cutoff_rate, self.device = float(radius), float(cutoff_rate), torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:   # (so that a tensor's device compares equal to it)
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self.virtual_channels < 1 or self.delta_t < 0 or not self.radius > 0:
+            raise ValueError("TrajectoryDataset: virtual_channels must be at least 1, delta_t at least 0 and radius positive")
+        self.keys, pos_parts, kinds, scaled, n_of, T_of = [], [], [], [], [], []
+        for key, position, kind in trajectories:
+            p, k = _as_host_tensor(position), _as_host_tensor(kind)
+            if p.dim() != 3 or p.size(2) != 3 or p.size(0) < 1:
+                raise ValueError(f"TrajectoryDataset: trajectory {key!r}: position must be [T,n,3] with T >= 1, got {list(p.shape)}")
+            if p.size(1) < 1:
+                raise ValueError(f"TrajectoryDataset: trajectory {key!r} is an empty cloud (position {list(p.shape)})")
+            if k.numel() != p.size(1):
+                raise ValueError(f"TrajectoryDataset: trajectory {key!r}: {k.numel()} kinds for {p.size(1)} particles")
+            k = k.to(self.device, torch.float32).reshape(-1, 1)
+            self.keys.append(key)
+            pos_parts.append(p)
+            kinds.append(k)
+            scaled.append(k / k.max())   # _node_feat's expression, once per trajectory
+            n_of.append(p.size(1))
+            T_of.append(p.size(0))
+        if not self.keys:
+            raise ValueError("TrajectoryDataset: no trajectory")
+        self.n_host, self.T_host = np.asarray(n_of, dtype=np.int64), np.asarray(T_of, dtype=np.int64)
+        self.row0_host = np.concatenate([[0], np.cumsum(self.n_host * self.T_host)[:-1]]).astype(np.int64)
+        self.kind0_host = np.concatenate([[0], np.cumsum(self.n_host)[:-1]]).astype(np.int64)
+        self.pos = torch.empty((int((self.n_host * self.T_host).sum()), 3), dtype=torch.float32, device=self.device)
+        for p, r0 in zip(pos_parts, self.row0_host):   # one trajectory at a time: no second copy of the whole set anywhere
+            self.pos[int(r0):int(r0) + p.size(0) * p.size(1)].copy_(p.reshape(-1, 3))
+        del pos_parts
+        self.kind, self.kind_scaled = torch.cat(kinds, 0).contiguous(), torch.cat(scaled, 0).contiguous()
+        self.row0, self.n, self.T, self.kind0 = (torch.from_numpy(a).to(self.device) for a in
+                                                 (self.row0_host, self.n_host, self.T_host, self.kind0_host))
+        step = max(1, self.delta_t)
+        if isinstance(samples, str):
+            if samples != "all":
+                raise ValueError(f"TrajectoryDataset: samples must be 'all' or an integer array [S,2], got {samples!r}")
+            samples = np.asarray([(t, f) for t, T in enumerate(self.T_host) for f in range(int(T) - step)], dtype=np.int64).reshape(-1, 2)
+        else:
+            samples = samples.detach().cpu().numpy() if isinstance(samples, torch.Tensor) else np.asarray(samples)
+            if samples.ndim != 2 or samples.shape[1] != 2 or samples.dtype.kind not in "iu":
+                raise ValueError(f"TrajectoryDataset: samples must be an integer array [S,2], got {samples.dtype} {list(samples.shape)}")
+            samples = samples.astype(np.int64)
+        if samples.shape[0] == 0:
+            raise ValueError("TrajectoryDataset: no sample (every trajectory is shorter than max(1, delta_t) + 1 frames?)")
+        t, f = samples[:, 0], samples[:, 1]
+        in_range = (t >= 0) & (t < len(self.keys))
+        bad = ~in_range | (f < 0) | (f + step > self.T_host[np.where(in_range, t, 0)] - 1)
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"TrajectoryDataset: sample {i} = (trajectory {int(t[i])}, start frame {int(f[i])}) is outside the data: "
+                             f"{len(self.keys)} trajectories, and a start frame f needs 0 <= f and f + {step} <= T - 1")
+        self.samples = np.ascontiguousarray(samples)
+        self.samples_dev = torch.from_numpy(self.samples).to(self.device)
+        self._node_cnt = self.n_host[t]
+        self.frames = [(self.keys[int(a)], int(b)) for a, b in self.samples]
+
+    @classmethod
+    def from_directory(cls, dataset_name, data_dir, virtual_channels, partition="train", max_samples=1e8, delta_t=15, cutoff_rate=0.0,
+                       device="cuda", seed=0, radius=None) -> "TrajectoryDataset":
+        """The samples ``Simulation(dataset_name, data_dir, ..., seed=seed)`` draws, without building their graphs: the same
+        ``read_trajectories`` pass and the same generator calls in the same order -- ``FRAMES_PER_TRAJECTORY`` start frames per
+        trajectory from ``[0, min(250, T - 1 - max(1, delta_t))]``, cut at ``max_samples``, then one permutation -- so ``ds.frames``
+        equals ``Simulation(...).frames`` and ``ds[i]`` equals ``Simulation(...)[i]``."""
+        rng = np.random.default_rng(seed)
+        delta_t, max_samples = int(delta_t), int(max_samples)
+        trajectories, samples = [], []
+        for key, position, particle_type in read_trajectories(os.path.join(data_dir, dataset_name), partition):
+            n_frames = min(Simulation.FRAMES_PER_TRAJECTORY, max_samples - len(samples))
+            last = min(250, np.asarray(position).shape[0] - 1 - max(1, delta_t))
+            drawn = rng.integers(0, last + 1, size=max(n_frames, 0))
+            samples.extend((len(trajectories), int(fr)) for fr in drawn)
+            trajectories.append((key, position, particle_type))
+            if len(samples) >= max_samples:
+                break
+        order = rng.permutation(len(samples))
+        samples = np.asarray(samples, dtype=np.int64).reshape(-1, 2)[order]
+        return cls(trajectories, virtual_channels, delta_t, Simulation.RADIUS if radius is None else radius, cutoff_rate, samples, device)
+
+    def __len__(self) -> int:
+        return self.samples.shape[0]
+
+    def __getitem__(self, i: int) -> Frame:
+        S = len(self)
+        i = int(i)
+        if not -S <= i < S:
+            raise IndexError(f"TrajectoryDataset: sample {i} of {S}")
+        t, f = (int(v) for v in self.samples[i % S])
+        n, r0, k0 = int(self.n_host[t]), int(self.row0_host[t]), int(self.kind0_host[t])
+        at = lambda frame: self.pos[r0 + frame * n:r0 + (frame + 1) * n]  # noqa: E731
+        return water3d_frame(at(f), at(f + 1) - at(f), at(f + self.delta_t), self.kind[k0:k0 + n], self.virtual_channels,
+                             self.radius, self.cutoff_rate)
+
+    def _assemble_nodes(self, ids_dev: torch.Tensor, ids_host: np.ndarray) -> dict:
+        """the node side of the batch of the samples ``ids_dev`` (device int64 [B]; ``ids_host``: the same on the host, already
+        validated): three device calls, sizes from the host's node counts, nothing uploaded or read back"""
+        B, dev, C = int(ids_host.size), self.device, self.virtual_channels
+        N = int(self._node_cnt[ids_host].sum())
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        out = {"loc_0": f32(N, 3), "loc_t": f32(N, 3), "vel_0": f32(N, 3), "node_feat": f32(N, 2), "node_attr": f32(N, 1),
+               "loc_mean": f32(B, 3, C), "batch": torch.empty(N, dtype=torch.int64, device=dev),
+               "ptr": torch.empty(B + 1, dtype=torch.int64, device=dev)}
+        slots = torch.empty((B, _TRAJ_SLOT_WORDS), dtype=torch.int64, device=dev)
+        ops = _TRAJ_OPS
+        ops.plan(ids_dev, self.samples_dev, self.row0, self.n, self.T, self.kind0, self.delta_t, out["ptr"], slots)
+        ops.gather(out["ptr"], slots, N, self.pos, self.kind, self.kind_scaled, *[out[k] for k in _NODE_KEYS], out["batch"])
+        ops.mean(out["ptr"], slots, self.pos, out["loc_mean"])
+        return out
+
+    def _assemble(self, ids_dev: torch.Tensor, ids_host: np.ndarray) -> Batch:
+        out = self._assemble_nodes(ids_dev, ids_host)
+        ptr_host = [0] + np.cumsum(self._node_cnt[ids_host]).tolist()
+        ei, dist = _TRAJ_OPS.edges(out["loc_0"], out["ptr"], ptr_host, self.radius, self.cutoff_rate)
+        out["edge_attr"], out["edge_index"] = dist.unsqueeze(-1), ei
+        return Batch(**{k: out[k] for k in _BATCH_KEYS})
+
+    def batch(self, ids) -> Batch:
+        """The ``Batch`` of the samples ``ids``: a sequence of ints, a numpy array, or an int64 tensor on either side, with values in
+        ``[0, len(self))`` (any order, repeats allowed), checked on the host as ``PackedDataset.batch`` does -- an id outside raises
+        IndexError.  Host ids are uploaded through pinned memory; a device tensor is used where it is, and checking it costs one
+        read-back (``TrajectoryLoader`` keeps both copies and pays neither)."""
+        ids_dev = None
+        if isinstance(ids, torch.Tensor):
+            if ids.device == self.device and ids.dtype == torch.int64 and ids.dim() == 1:
+                ids_dev = ids.contiguous()
+            ids = ids.detach().cpu().numpy()
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or ids.size == 0:
+            raise ValueError("TrajectoryDataset.batch: ids must be a non-empty 1-D sequence")
+        if ids.dtype.kind not in "iu":
+            raise ValueError(f"TrajectoryDataset.batch: ids must be integers, got {ids.dtype}")
+        ids = ids.astype(np.int64)
+        if ids.min() < 0 or ids.max() >= len(self):
+            raise IndexError(f"TrajectoryDataset.batch: ids span [{ids.min()}, {ids.max()}] but there are {len(self)} samples")
+        if ids_dev is None or self.device.type != "cuda":
+            ids_dev = _upload_ids(torch.from_numpy(ids), self.device)
+        return self._assemble(ids_dev, ids)
+
+
+class TrajectoryLoader:
+    """``DataLoader`` over a ``TrajectoryDataset``, as ``PackedLoader`` is over a packed one: same batching, same
+    ``torch.randperm(n, generator=...)`` order (equal generators give the samples of ``DataLoader(ds, ...)``'s batches in the same
+    order).  The epoch's order is uploaded ONCE, through pinned memory with a non-blocking copy; every batch hands the kernels a slice
+    of that device tensor.  A batch is the three launches of its node side plus the batched graph build, whose read-back of the edge
+    counts is the only synchronisation.  ``state_dict`` / ``load_state_dict`` hold the generator, so ``save_checkpoint(loaders=...)``
+    and ``fit(resume=True)`` take the loader as they take the others."""
+
+    def __init__(self, ds: TrajectoryDataset, batch_size=1, shuffle=False, drop_last=False, generator: Optional[torch.Generator] = None):
+        self.dataset, self.batch_size, self.shuffle, self.drop_last, self.generator = ds, int(batch_size), shuffle, drop_last, generator
+
+    def __len__(self) -> int:
+        n = len(self.dataset)
+        return n // self.batch_size if self.drop_last else math.ceil(n / self.batch_size)
+
+    def __iter__(self) -> Iterator[Batch]:
+        n = len(self.dataset)
+        order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
+        ids_dev, order_host = _upload_ids(order, self.dataset.device), order.numpy()
+        for i in range(len(self)):
+            a, b = i * self.batch_size, min((i + 1) * self.batch_size, n)
+            yield self.dataset._assemble(ids_dev[a:b], order_host[a:b])
+
+    def state_dict(self) -> dict:
+        return _generator_state(self.generator)
+
+    def load_state_dict(self, state) -> None:
+        _load_generator_state(self.generator, state, "TrajectoryLoader")

@@ -718,6 +718,44 @@ int fastegnn_collate_gather_uniform(const int64_t *ids, int32_t B, int32_t n_fra
                                     int32_t *rowptr, int32_t *erow, int32_t *col, int32_t *perm, int32_t *cscptr, int32_t *csc_eid,
                                     int32_t *chunk_row, int32_t *n_chunks, void *stream);
 
+/* ---- mini-batch assembly from device-resident trajectories (datasets/simulation/dataset.py:71-93, datasets/protein/dataset.py:81-173) ----
+ * ADDITIVE exports, found by symbol: FASTEGNN_ABI_VERSION stays 108.
+ * A trajectory dataset keeps the POSITIONS, not the graphs made of them: pos fp32 [pos_rows, 3] holds every trajectory frame after
+ * frame (trajectory t: rows traj_row0[t] + f * traj_n[t] .. of frame f < traj_T[t]); kind / kind_scaled fp32 [kind_rows] hold the
+ * particle kinds of trajectory t (and kind / max kind) at traj_kind0[t] ..; traj_row0 / traj_n / traj_T / traj_kind0 are int64
+ * [n_traj], samples int64 [n_samples, 2] = (trajectory, start frame), all on the device.  A batch is the B samples ids[0 .. B)
+ * (int64, device; any order, repeats allowed); slot i of it is the cloud of n nodes of sample ids[i] = (t, f):
+ *   loc_0 = pos[f], vel_0 = pos[f+1] - pos[f], loc_t = pos[f+delta_t], node_feat = [|vel_0|, kind_scaled], node_attr = kind.
+ * Its node side is three launches whatever B is; none reads anything back, synchronises, allocates or uses an atomic, and the only
+ * workspace is the slot table.
+ *   _plan    ptr_out int64 [B+1]: exclusive prefix sums of the samples' node counts (the batch's `ptr`); slots_out int64
+ *            [B, FASTEGNN_TRAJ_SLOT_WORDS]: first source row in pos of frames f, f+1, f+delta_t and first row in kind.  One workgroup,
+ *            1024 samples per round with a running carry: any B.
+ *   _gather  ONE launch over the n_nodes_out nodes (one node per lane, tiles of 1024; a tile finds the slots it touches by binary
+ *            search in ptr, a tile inside one slot searches nothing per node): loc_0, loc_t, vel_0 fp32 [n,3], node_feat [n,2],
+ *            node_attr [n,1], batch_out int64 [n] = the node's slot.  vel_0 is one fp32 subtraction per component;
+ *            node_feat[:,0] = sqrt((vx*vx + vy*vy) + vz*vz) with every operation rounded to fp32 by itself (no fused multiply-add)
+ *            and a correctly rounded square root; the rest are copies.  n_nodes_out is the caller's, from its host copy of the node
+ *            counts, and must equal ptr[B].
+ *   _mean    one workgroup of 256 threads per slot: loc_mean fp32 [B,3,C], every [b,k,:] = the sum of the slot's loc_0[:,k] in fp64
+ *            (thread t adds nodes t, t+256, .. in ascending order, the 256 partial sums are added pairwise over strides 128 .. 1: an
+ *            order that depends on the node count alone), divided by n in fp64, rounded to fp32, repeated C times.  A slot without
+ *            nodes gives 0.
+ * _plan clamps sample ids to [0, n_samples), trajectory numbers to [0, n_traj) and frame numbers (f, f+1, f+delta_t each) to [0, T);
+ * _gather and _mean skip a slot whose source rows do not lie inside [0, pos_rows) / [0, kind_rows): nothing is read outside the
+ * tables and nothing is written beyond n_nodes_out rows (B rows of loc_mean), whatever the device arrays hold.  B == 0 or
+ * n_nodes_out == 0: _gather launches nothing.  FASTEGNN_E_INVALID before any launch for: B < 0, n_samples < 1, n_traj < 1,
+ * delta_t < 0, a negative size, C outside 1 .. 2^20, nodes asked for from an empty table, a null pointer that would be used. */
+#define FASTEGNN_TRAJ_SLOT_WORDS 4
+int fastegnn_traj_plan(const int64_t *ids, int32_t B, const int64_t *samples, int64_t n_samples, const int64_t *traj_row0,
+                       const int64_t *traj_n, const int64_t *traj_T, const int64_t *traj_kind0, int32_t n_traj, int32_t delta_t,
+                       int64_t *ptr_out, int64_t *slots_out, void *stream);
+int fastegnn_traj_gather(const int64_t *ptr, const int64_t *slots, int32_t B, int64_t n_nodes_out, const float *pos, int64_t pos_rows,
+                         const float *kind, const float *kind_scaled, int64_t kind_rows, float *loc_0, float *loc_t, float *vel_0,
+                         float *node_feat, float *node_attr, int64_t *batch_out, void *stream);
+int fastegnn_traj_mean(const int64_t *ptr, const int64_t *slots, int32_t B, const float *pos, int64_t pos_rows, int32_t C,
+                       float *loc_mean, void *stream);
+
 /* ---- exchange steps of the sharded path (the reference has no distributed code) ----
  * RCCL collectives behind the C ABI: every call is enqueued on `stream` (ordered with the stage kernels, capturable
  * into a HIP graph) and returns at once.  RCCL is bound at run time (dlopen; FASTEGNN_E_NODEVICE when absent).
