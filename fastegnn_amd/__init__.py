@@ -8,6 +8,7 @@ from .egnn import EGNN  # noqa: F401
 from .fastrf import FastRF  # noqa: F401
 from .train import FusedAdam, MMDSampler, evaluate, train_epoch, train_step  # noqa: F401
 from .checkpoint import fit, load_checkpoint, save_checkpoint  # noqa: F401
+from .rollout import Rollout, rollout  # noqa: F401
 
 __all__ = ["FastEGNN", "FastRF", "EGNN", "SortedGraph", "FusedAdam", "MMDSampler", "train_step", "train_epoch", "evaluate",
-           "fit", "save_checkpoint", "load_checkpoint"]
+           "fit", "save_checkpoint", "load_checkpoint", "Rollout", "rollout"]

@@ -1038,6 +1038,10 @@ class TrajectoryDataset:
         ``[0, len(self))`` (any order, repeats allowed), checked on the host as ``PackedDataset.batch`` does -- an id outside raises
         IndexError.  Host ids are uploaded through pinned memory; a device tensor is used where it is, and checking it costs one
         read-back (``TrajectoryLoader`` keeps both copies and pays neither)."""
+        return self._assemble(*self._checked_ids(ids))
+
+    def _checked_ids(self, ids, who: str = "TrajectoryDataset.batch"):
+        """``batch``'s validation of ``ids`` -> (the ids on the device, the same as a host int64 array)"""
         ids_dev = None
         if isinstance(ids, torch.Tensor):
             if ids.device == self.device and ids.dtype == torch.int64 and ids.dim() == 1:
@@ -1045,15 +1049,15 @@ class TrajectoryDataset:
             ids = ids.detach().cpu().numpy()
         ids = np.asarray(ids)
         if ids.ndim != 1 or ids.size == 0:
-            raise ValueError("TrajectoryDataset.batch: ids must be a non-empty 1-D sequence")
+            raise ValueError(f"{who}: ids must be a non-empty 1-D sequence")
         if ids.dtype.kind not in "iu":
-            raise ValueError(f"TrajectoryDataset.batch: ids must be integers, got {ids.dtype}")
+            raise ValueError(f"{who}: ids must be integers, got {ids.dtype}")
         ids = ids.astype(np.int64)
         if ids.min() < 0 or ids.max() >= len(self):
-            raise IndexError(f"TrajectoryDataset.batch: ids span [{ids.min()}, {ids.max()}] but there are {len(self)} samples")
+            raise IndexError(f"{who}: ids span [{ids.min()}, {ids.max()}] but there are {len(self)} samples")
         if ids_dev is None or self.device.type != "cuda":
             ids_dev = _upload_ids(torch.from_numpy(ids), self.device)
-        return self._assemble(ids_dev, ids)
+        return ids_dev, ids
 
 
 class TrajectoryLoader:

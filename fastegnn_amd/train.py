@@ -505,6 +505,16 @@ def train_step(model, optimizer: FusedAdam, data: dict, sample_nodes, sigma, wei
     return loss, mse
 
 
+def _predict(model, data, edge_attr):
+    """the model call of a forward-only pass on the batch ``data`` with its augmented ``edge_attr`` -> (loc_pred, vloc); ``EGNN`` is
+    called by its own signature (utils/train.py:66-68) and has no virtual nodes: vloc is None.  (``evaluate`` and ``rollout``)"""
+    if type(model).__name__ == "EGNN":
+        out = model(x=data["loc_0"], h=data["node_feat"], edge_index=_graph_or_edges(data), edge_fea=edge_attr, v=data["vel_0"])
+        return out[0], None
+    return model(node_loc=data["loc_0"], node_vel=data["vel_0"], node_attr=None, node_feat=data["node_feat"],
+                 edge_index=_graph_or_edges(data), loc_mean=data["loc_mean"], data_batch=data["batch"], edge_attr=edge_attr)
+
+
 def _evaluate_pass(model, loader, sigma, weight, sampler, num_sample):
     """one forward-only sweep over the loader -> the device accumulator (None for an empty loader); nothing is read back"""
     acc = None
@@ -514,13 +524,11 @@ def _evaluate_pass(model, loader, sigma, weight, sampler, num_sample):
         if acc is None:
             acc = torch.zeros(3, dtype=torch.float64, device=loc_0.device)
         edge_attr = augment_edge_attr(data.get("edge_attr"), loc_0, data["edge_index"])
-        if egnn:   # utils/train.py:66-68: no virtual nodes, no MMD term
-            out = model(x=loc_0, h=data["node_feat"], edge_index=_graph_or_edges(data), edge_fea=edge_attr, v=data["vel_0"])
+        loc_pred, vloc = _predict(model, data, edge_attr)
+        if egnn:   # no virtual nodes, no MMD term
             n_graphs = data["ptr"].numel() - 1 if "ptr" in data else data["loc_mean"].size(0)
-            mse_mmd_eval(out[0], n_graphs, data["loc_t"], acc, sigma, weight)
+            mse_mmd_eval(loc_pred, n_graphs, data["loc_t"], acc, sigma, weight)
             continue
-        loc_pred, vloc = model(node_loc=loc_0, node_vel=data["vel_0"], node_attr=None, node_feat=data["node_feat"],
-                               edge_index=_graph_or_edges(data), loc_mean=data["loc_mean"], data_batch=data["batch"], edge_attr=edge_attr)
         nodes = count = None
         if sampler is not None:
             nodes, count = sampler.draw(data["ptr"], min(int(num_sample), loc_0.size(0)))

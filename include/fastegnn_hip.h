@@ -756,6 +756,41 @@ int fastegnn_traj_gather(const int64_t *ptr, const int64_t *slots, int32_t B, in
 int fastegnn_traj_mean(const int64_t *ptr, const int64_t *slots, int32_t B, const float *pos, int64_t pos_rows, int32_t C,
                        float *loc_mean, void *stream);
 
+/* ---- rollouts: the state update between two forwards of a model that is fed its own prediction (fastegnn_amd/rollout.py) ----
+ * ADDITIVE exports, found by symbol: FASTEGNN_ABI_VERSION stays 108.  The project's own semantics (the reference has no rollout).
+ * A rollout of the B samples ids[0 .. B) = (trajectory t, start frame f) of the tables above, with stride delta_t >= 1, starts from the
+ * node tensors of fastegnn_traj_gather / _mean; step k = 0, 1, .. hands the model the state and gets x_new fp32 [n_nodes,3], its
+ * prediction of frame f + (k+1) delta_t.  The state is then advanced by TWO launches whatever B is; none reads anything back,
+ * synchronises, allocates or uses an atomic, and both are capturable:
+ *   _advance  ONE launch over the n_nodes nodes, one node per lane, tail masked; per component
+ *               vel = (x_new - loc) * (1.0f / delta_t)   one fp32 subtraction, then one fp32 multiplication, no fused multiply-add
+ *               loc = x_new                              (in place: `loc` holds x_cur on entry; x_new must not alias it)
+ *             and node_feat[:,0] = sqrt((vx*vx + vy*vy) + vz*vz) by _gather's rule; node_feat[:,1] is not touched.  `record`, when not
+ *             null, is fp32 [n_nodes,3] and receives x_new as it came.  A NON-FINITE component of x_new does not enter the state: loc
+ *             keeps its value, the vel component is 0, and the int32 word `flag` (device or host-mapped, fastegnn_host_words_alloc)
+ *             gets a plain store of the constant 1 -- an all-finite call leaves it alone; `record` still gets the raw value.
+ *   _graph    one workgroup of 256 threads per graph b (nodes ptr[b] .. ptr[b+1]): loc_mean fp32 [B,3,C] of `loc` by _mean's rule (the
+ *             bits fastegnn_traj_mean gives on the same rows) and, in the same pass, when `sse` is not null,
+ *               sse[b] = sum over the graph's nodes of (dx*dx + dy*dy) + dz*dz,  d = (double)x_new - (double)pos[truth_rows[b] + i]
+ *             in fp64, every operation rounded by itself, summed in _mean's order (thread t takes nodes t, t+256, .., then the pairwise
+ *             tree).  sse[b] = NaN where truth_rows[b] < 0 (no truth frame), where truth_rows[b] .. + n does not lie inside
+ *             [0, pos_rows), or where the graph has no node.  A graph whose node range does not lie inside [0, n_nodes) counts as
+ *             empty (loc_mean 0).  sse null: x_new, pos and truth_rows are not read.  The caller passes row k of its [steps,B] tables.
+ * and once per rollout
+ *   _plan     ONE launch: truth_rows int64 [steps,B], [k,b] = the first row in pos of frame f + (k+1) delta_t of slot b, or -1 where that
+ *             frame is not below T.  Sample ids, trajectory numbers and start frames are clamped as fastegnn_traj_plan clamps them;
+ *             nothing is uploaded.
+ * Nothing is read outside the tables and nothing is written beyond n_nodes rows (B rows of loc_mean / sse, steps * B words of
+ * truth_rows), whatever the device arrays hold.  FASTEGNN_E_INVALID before any launch for: a negative size, steps < 1, delta_t < 1,
+ * n_samples < 1, n_traj < 1, C outside 1 .. 2^20, a null pointer that would be used (`flag` always). */
+int fastegnn_rollout_plan(const int64_t *ids, int32_t B, const int64_t *samples, int64_t n_samples, const int64_t *traj_row0,
+                          const int64_t *traj_n, const int64_t *traj_T, int32_t n_traj, int32_t delta_t, int32_t steps,
+                          int64_t *truth_rows, void *stream);
+int fastegnn_rollout_advance(const float *x_new, int64_t n_nodes, int32_t delta_t, float *loc, float *vel, float *node_feat,
+                             float *record, int32_t *flag, void *stream);
+int fastegnn_rollout_graph(const int64_t *ptr, int32_t B, const float *loc, const float *x_new, int64_t n_nodes, const float *pos,
+                           int64_t pos_rows, const int64_t *truth_rows, int32_t C, float *loc_mean, double *sse, void *stream);
+
 /* ---- exchange steps of the sharded path (the reference has no distributed code) ----
  * RCCL collectives behind the C ABI: every call is enqueued on `stream` (ordered with the stage kernels, capturable
  * into a HIP graph) and returns at once.  RCCL is bound at run time (dlopen; FASTEGNN_E_NODEVICE when absent).
