@@ -1,4 +1,7 @@
 // extern "C" surface of libfastegnn_hip.so (declared in include/fastegnn_hip.h).
+#include <atomic>
+#include <cstdint>
+#include <cstdlib>
 #include <vector>
 #include "kernels.h"
 #include <initializer_list>
@@ -45,6 +48,17 @@ void prof_end(int id, hipStream_t st) {
   (void)hipEventRecord(e, st);
   g_recs.push_back({id, g_open[id], e});
 }
+
+// FASTEGNN_KEEP_DEAD_EDGE_WORK=1 (DIAGNOSTIC, read per call): the layer calls run every stage as the staged entry points do -- aggm
+// written, the zero rows of g_h / g_aggm filled and read, every gradient pointer required (a null g_x / g_Z is the "null buffer" error it
+// was).  The baseline the specialised paths are tested and measured against.
+static bool keep_dead_edge_work() {
+  const char *v = getenv("FASTEGNN_KEEP_DEAD_EDGE_WORK");
+  return v && v[0] && !(v[0] == '0' && !v[1]);
+}
+// host-side counts of layer calls per specialised path (fastegnn_path_counts); relaxed atomics: layer calls may come from several host threads
+static std::atomic<int64_t> g_path_counts[FASTEGNN_PATH_COUNT];
+static void count_path(int id) { g_path_counts[id].fetch_add(1, std::memory_order_relaxed); }
 
 static int check_layer(const fastegnn_layer_t *L, const char *who) {
   if (!L) {
@@ -218,6 +232,14 @@ int fastegnn_profile_collect(double *total_ms, int64_t *launches) {
   return FASTEGNN_OK;
 }
 
+int fastegnn_path_counts(int64_t *out, int32_t reset) {
+  if (!out) { set_error("fastegnn_path_counts: null output"); return FASTEGNN_E_INVALID; }
+  for (int i = 0; i < FASTEGNN_PATH_COUNT; ++i) {
+    out[i] = reset ? g_path_counts[i].exchange(0, std::memory_order_relaxed) : g_path_counts[i].load(std::memory_order_relaxed);
+  }
+  return FASTEGNN_OK;
+}
+
 int fastegnn_layer_forward(const fastegnn_layer_t *L, void *stream) {
   int rc = check_layer(L, "fastegnn_layer_forward");
   if (rc) return rc;
@@ -233,9 +255,13 @@ int fastegnn_layer_forward(const fastegnn_layer_t *L, void *stream) {
   FE_REQUIRE(L->aggm, "fastegnn_layer_forward: aggm null");
   if ((rc = graph_xsum_partials(L, L->aggm, st))) return rc;
   if ((rc = graph_pre_forward(L, st, L->aggm))) return rc;
-  if ((rc = edge_forward(L, st))) return rc;
+  // h_out == NULL && HvT_out == NULL: no node update, and aggm feeds nothing else -- the edge stage does not build it
+  const bool no_aggm = !has(L, FASTEGNN_F_RF) && !L->h_out && !L->HvT_out && !keep_dead_edge_work();
+  if ((rc = edge_forward(L, st, !no_aggm))) return rc;
   if ((rc = virt_forward(L, st, true))) return rc;
-  return graph_post_forward(L, st);
+  if ((rc = graph_post_forward(L, st))) return rc;
+  if (no_aggm) count_path(FASTEGNN_PATH_NO_AGGM);
+  return FASTEGNN_OK;
 }
 
 int fastegnn_layer_backward(const fastegnn_layer_t *L, void *stream) {
@@ -252,6 +278,13 @@ int fastegnn_layer_backward(const fastegnn_layer_t *L, void *stream) {
   auto guard_virt = [&]() { return guard_stage(L, wb, G_VIRT); };
   auto guard_edge = [&]() { return guard_stage(L, wb, G_EDGE); };
   auto guard_node_pre = [&]() { return guard_stage(L, wb, G_NODE_PRE); };
+  const bool keep = keep_dead_edge_work();
+  // g_x == NULL / g_Z == NULL: that input gradient is not wanted (include/fastegnn_hip.h) -- FastEGNN wiring with the atomic scatter only
+  // (the EGNN baseline has no Z: its g_Z is null anyway)
+  FE_REQUIRE(keep || !((!L->g_x && (L->flags & (FASTEGNN_F_RF | FASTEGNN_F_DETERMINISTIC | FASTEGNN_F_EGNN))) ||
+                       (!L->g_Z && (L->flags & (FASTEGNN_F_RF | FASTEGNN_F_DETERMINISTIC)) && !has(L, FASTEGNN_F_EGNN))),
+             "fastegnn_layer_backward: a null g_x / g_Z (gradient not wanted) is not combined with FASTEGNN_F_DETERMINISTIC, FASTEGNN_F_RF "
+             "or FASTEGNN_F_EGNN");
   if (has(L, FASTEGNN_F_EGNN)) {
     if ((rc = guard_virt())) return rc;
     if ((rc = virt_backward(L, st, &wb))) return rc;
@@ -262,17 +295,33 @@ int fastegnn_layer_backward(const fastegnn_layer_t *L, void *stream) {
     if ((rc = node_pre_backward(L, st, &wb))) return rc;
     return wb.finish();
   }
-  if ((rc = graph_post_backward(L, st, &wb, true))) return rc;   // (+ the zeroing of g_Bc / g_Zp for the virtual stage)
+  // g_h_out == NULL && g_HvT_out == NULL: no gradient arrives for h / Hv, so g_aggm and this layer's own part of g_h are zero rows --
+  // neither filled by the virtual stage nor read by the edge and node_pre stages
+  BwdSkip skip;
+  if (!keep) {
+    skip.dead_rows = !has(L, FASTEGNN_F_RF) && !L->g_h_out && !L->g_HvT_out;
+    skip.no_gx = !L->g_x;
+    skip.no_gz = !L->g_Z;
+    // the two-line scatter rows (measured: profiles/dead_edge_work.txt, section 3): this call both scatters into g_QX_src and reads it back (one GPU, no second launch adding into it)
+    skip.split_gqx = L->g_QX && L->g_QX == L->g_QX_src && L->graph.n_src == L->N &&
+                     !(L->flags & (FASTEGNN_F_DETERMINISTIC | FASTEGNN_F_GQX_ACCUM | FASTEGNN_F_RF)) &&
+                     reinterpret_cast<uintptr_t>(L->g_QX_src) % 128 == 0;
+  }
+  if ((rc = graph_post_backward(L, st, &wb, true, skip))) return rc;   // (+ the zeroing of g_Bc / g_Zp for the virtual stage)
   if ((rc = guard_virt())) return rc;
-  if ((rc = virt_backward(L, st, &wb, true))) return rc;
+  if ((rc = virt_backward(L, st, &wb, true, skip))) return rc;
   if ((rc = guard_stage(L, wb, G_GRAPH_PRE))) return rc;
-  if ((rc = graph_pre_backward(L, st, &wb))) return rc;
+  if ((rc = graph_pre_backward(L, st, &wb, skip))) return rc;
   if ((rc = guard_edge())) return rc;
-  if ((rc = edge_backward(L, st, &wb))) return rc;
+  if ((rc = edge_backward(L, st, &wb, skip))) return rc;
   if ((rc = edge_col_reduce(L, st))) return rc;
   if ((rc = guard_node_pre())) return rc;
-  if ((rc = node_pre_backward(L, st, &wb))) return rc;
-  return wb.finish();
+  if ((rc = node_pre_backward(L, st, &wb, skip))) return rc;
+  if ((rc = wb.finish())) return rc;
+  if (skip.dead_rows) count_path(FASTEGNN_PATH_ZERO_GAGGM);
+  if (skip.no_gx) count_path(FASTEGNN_PATH_NO_GX);
+  if (skip.split_gqx) count_path(FASTEGNN_PATH_SPLIT_GQX);
+  return FASTEGNN_OK;
 }
 
 }  // extern "C"

@@ -102,24 +102,43 @@ int graph_xsum(const fastegnn_layer_t *L, hipStream_t st);
 // `part`, graph_pre_forward(part != null) combines them into L->xsum itself and zeroes poolV / poolX for virt_forward(pools_zeroed).
 int graph_xsum_partials(const fastegnn_layer_t *L, float *part, hipStream_t st);
 int graph_pre_forward(const fastegnn_layer_t *L, hipStream_t st, float *part = nullptr);
-int edge_forward(const fastegnn_layer_t *L, hipStream_t st);
+// aggm = false (the layer call of a layer without a node update): aggm is not written (edge_fwd_kernel<MODE, false>)
+int edge_forward(const fastegnn_layer_t *L, hipStream_t st, bool aggm = true);
 int virt_forward(const fastegnn_layer_t *L, hipStream_t st, bool pools_zeroed = false);
 int graph_post_forward(const fastegnn_layer_t *L, hipStream_t st);
 // `shared`: a weight-gradient batch that outlives the stage (fastegnn_layer_backward: ONE contraction launch and ONE
 // reduction launch per layer instead of one pair per stage); null: the stage contracts and reduces its own jobs.
 // zero_acc: the stage also zeroes g_Bc / g_Zp, the accumulators of the virtual stage that follows it in the layer call
 // (virt_backward(acc_zeroed) then issues no fills of its own)
-int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, bool zero_acc = false);
-int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, bool acc_zeroed = false);
-int graph_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr);
-int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr);
+// What fastegnn_layer_backward leaves out of a layer (include/fastegnn_hip.h); the staged entry points pass none of it: they fill, read
+// and require every buffer.
+struct BwdSkip {
+  bool dead_rows = false;   // g_h_out == NULL && g_HvT_out == NULL: this layer's own part of g_h is zero rows -- not filled by the virtual
+                            // stage, not read by node_pre; g_aggm (zero rows as well) is a plain fill, the edge stage reads it
+  bool no_gx = false;       // g_x == NULL: d loss / d x of the layer inputs is not wanted -- nothing forms, carries or writes it;
+                            // g_xrow and g_xbar stay untouched
+  bool no_gz = false;       // g_Z == NULL: g_Zp is not needed and the graph stages write no g_Z
+  bool split_gqx = false;   // g_QX_src holds a Q block [N,64] and an x block [N,4] behind it (the same N * QXLD floats) instead of rows of
+                            // Q | x | pad: the 256-byte atomic row of an edge lies in two 128-byte lines instead of three
+};
+// the two layouts of g_QX_src as (row stride of the Q part, offset of the x part, row stride of the x part), in floats
+struct GqxLayout { unsigned q_ld, x_off, x_ld; };
+inline GqxLayout gqx_layout(bool split, int N) {
+  return split ? GqxLayout{(unsigned)H, (unsigned)N * H, 4u} : GqxLayout{(unsigned)QXLD, (unsigned)H, (unsigned)QXLD};
+}
+int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, bool zero_acc = false,
+                        const BwdSkip &skip = BwdSkip());
+int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, bool acc_zeroed = false,
+                  const BwdSkip &skip = BwdSkip());
+int graph_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, const BwdSkip &skip = BwdSkip());
+int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, const BwdSkip &skip = BwdSkip());
 // virt_bwd.hip: floats of wg_virt for B4 (1 <= C <= 64)
 size_t virt_pc_wg_floats(size_t N, size_t C);
 // the channel-phased form of B4 (virt_bwd_cs_kernel): does it run for this shape, and its share of wg_virt
 bool virt_cs_applies(long N, int C, int flags);
 size_t virt_cs_wg_floats(size_t C);
 int edge_col_reduce(const fastegnn_layer_t *L, hipStream_t st);
-int node_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr);
+int node_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared = nullptr, const BwdSkip &skip = BwdSkip());
 // operand regions of the node-level / graph-level weight gradients inside wg_node (disjoint, so that the jobs of a whole
 // layer can be contracted together): [0,2M) virt, [2M,4M) node_pre, [4M,7M) graph_post, [7M,8M) graph_pre rows of 64 floats,
 // M = max(N, B*C)

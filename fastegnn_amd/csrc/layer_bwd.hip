@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void graph_post_bwd_kernel(GraphPostBwdArgs a)
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.B * 3 * a.C; i += gridDim.x * blockDim.x) {
     const int b = i / (3 * a.C);
     const float g = a.g_Z_out[i];
-    a.g_Z[i] = g;
+    if (a.g_Z) a.g_Z[i] = g;   // (null: d loss / d Z is not wanted, fastegnn_layer_backward)
     a.g_poolX[i] = g / fmaxf(a.xsum[b * 4 + 3], 1.f);
   }
   if (a.flags & FASTEGNN_F_RF) {   // identity on the virtual features: no pooled-message gradient
@@ -116,25 +116,25 @@ __global__ __launch_bounds__(256) void graph_post_bwd_coords_kernel(const float 
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 3 * C; i += gridDim.x * blockDim.x) {
     const int b = i / (3 * C);
     const float g = g_Z_out[i];
-    g_Z[i] = g;
+    if (g_Z) g_Z[i] = g;
     g_poolX[i] = g / fmaxf(xsum[b * 4 + 3], 1.f);
   }
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * C * H; i += gridDim.x * blockDim.x) g_HvT[i] = 0.f;
 }
 
-int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, bool zero_acc) {
+int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, bool zero_acc, const BwdSkip &skip) {
   FE_REQUIRE(!zero_acc || (L->g_Bc && L->g_Zp), "graph_post_backward: g_Bc / g_Zp null");
   float *z_Bc = zero_acc ? L->g_Bc : nullptr, *z_Zp = zero_acc ? L->g_Zp : nullptr;
   if (!L->g_HvT_out && !has(L, FASTEGNN_F_RF)) {
     FE_REQUIRE(!L->g_h_out, "graph_post_backward: g_HvT_out is null and g_h_out is not (both null: no gradient for h / Hv; otherwise neither)");
-    FE_REQUIRE(L->xsum && L->g_Z_out && L->g_Z && L->g_HvT && L->g_poolX, "graph_post_backward: null buffer");
+    FE_REQUIRE(L->xsum && L->g_Z_out && (L->g_Z || skip.no_gz) && L->g_HvT && L->g_poolX, "graph_post_backward: null buffer");
     int grid = cdiv((long)L->B * L->C * H, 256);
     if (grid > 256) grid = 256;
     if (grid < 1) grid = 1;
     { ProfScope _ps_graph_post_bwd_kernel(K_GRAPH_POST_BWD, st); hipLaunchKernelGGL(graph_post_bwd_coords_kernel, dim3(grid), dim3(256), 0, st, L->xsum, L->g_Z_out, L->g_Z, L->g_poolX, L->g_HvT, L->B, L->C, z_Bc, z_Zp); }
     return check_launch("graph_post_bwd_coords_kernel");   // no node_mlp_virtual jobs: their gradients are not defined
   }
-  FE_REQUIRE(L->xsum && L->HvT && L->poolV && L->g_Z_out && L->g_HvT_out && L->g_Z && L->g_HvT && L->g_poolV &&
+  FE_REQUIRE(L->xsum && L->HvT && L->poolV && L->g_Z_out && L->g_HvT_out && (L->g_Z || skip.no_gz) && L->g_HvT && L->g_poolV &&
                  L->g_poolX && L->wg_node && L->grads && L->wpack,
              "graph_post_backward: null buffer");
   const long M = (long)L->B * L->C;
@@ -168,7 +168,7 @@ int graph_post_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *s
 // =====================================================================================
 struct GraphPreBwdArgs {
   const float *xsum, *Z, *g_Bc, *g_Zp, *V0W;
-  float *g_Z, *g_HvT, *g_xbar, *wg_mxt;
+  float *g_Z, *g_HvT, *g_xbar, *wg_mxt;   // g_Z / g_xbar null: not wanted, not written (fastegnn_layer_backward)
   int B, C, bf16;
 };
 // grid (B, GPB_SPLIT): the per-(channel, feature) outputs of a graph are dealt to GPB_SPLIT workgroups; each of them
@@ -226,21 +226,22 @@ __global__ __launch_bounds__(256) void graph_pre_bwd_kernel(GraphPreBwdArgs a) {
     float acc = 0.f;
     for (int d = 0; d < C; ++d) acc += (gmX[c * C + d] + gmX[d * C + c]) * mz[k * C + d];
     gmz[i] = acc;
-    if (i % gridDim.y == blockIdx.y) a.g_Z[(size_t)b * 3 * C + i] += acc + a.g_Zp[(size_t)b * 3 * C + i];
+    if (a.g_Z && i % gridDim.y == blockIdx.y) a.g_Z[(size_t)b * 3 * C + i] += acc + a.g_Zp[(size_t)b * 3 * C + i];
   }
   __syncthreads();
-  if (threadIdx.x < 3 && blockIdx.y == 0) {
+  if (a.g_xbar && threadIdx.x < 3 && blockIdx.y == 0) {
     float acc = 0.f;
     for (int c = 0; c < C; ++c) acc += gmz[threadIdx.x * C + c];
     a.g_xbar[b * 3 + threadIdx.x] = -acc / cnt;
   }
 }
-int graph_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared) {
-  FE_REQUIRE(L->xsum && L->Z && L->HvT && L->g_Bc && L->g_Zp && L->g_Z && L->g_HvT && L->g_xbar && L->wg_node && L->grads,
+int graph_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, const BwdSkip &skip) {
+  FE_REQUIRE(L->xsum && L->Z && L->HvT && L->g_Bc && L->g_Zp && (L->g_Z || skip.no_gz) && L->g_HvT && L->g_xbar && L->wg_node && L->grads,
              "graph_pre_backward: null buffer");
   const long M = (long)L->B * L->C;
   float *wg_mxt = L->wg_node + 7 * wg_node_rows(L) * H;   // this stage's operand region of wg_node (kernels.h)
-  GraphPreBwdArgs a{L->xsum, L->Z, L->g_Bc, L->g_Zp, L->params[FASTEGNN_P_VIRT0_W], L->g_Z, L->g_HvT, L->g_xbar, wg_mxt,
+  GraphPreBwdArgs a{L->xsum, L->Z, L->g_Bc, L->g_Zp, L->params[FASTEGNN_P_VIRT0_W], skip.no_gz ? nullptr : L->g_Z, L->g_HvT,
+                    skip.no_gx ? nullptr : L->g_xbar, wg_mxt,
                     L->B, L->C, has(L, FASTEGNN_F_BF16) ? 1 : 0};
   const size_t lds = graph_pre_bwd_lds_floats(L->C) * sizeof(float);
   { ProfScope _ps_graph_pre_bwd_kernel(K_GRAPH_PRE_BWD, st); hipLaunchKernelGGL(graph_pre_bwd_kernel, dim3(L->B, GPB_SPLIT), dim3(256), lds, st, a); }
@@ -273,6 +274,7 @@ struct EdgeBwdArgs {
   float *slab, *slab_b;   // producer/consumer variant: partial slabs of the two in-kernel weight gradients
   int slab_w2, slab_wx1;
   float *cons_scratch;    // [grid][2][64*64] running sums of the two consumers, accumulator order (wg_edge)
+  GqxLayout gqx;          // layout of g_QXs_atomic (kernels.h)
 };
 #ifndef FE_PC_PRIO
 #define FE_PC_PRIO 3
@@ -331,7 +333,11 @@ __device__ __forceinline__ void pc_tile_store(float *tile, int j, int q, const V
 // EA: edge_attr slots whose weight-column sums are accumulated in the row walk, without guards (2 covers edge_attr_nf <= 2 --
 // every BASELINE configuration --, 7 the rest): a per-slot `k < ea_dim` test inside the 16-edge walk compiled into ~130
 // scalar branches per tile and made the walk 23 % of the producers' time (phase stamps).
-template <int MODE, int EA>
+// GX = false (the layer call with g_x == NULL, atomic scatter only): d loss / d x of the layer inputs is not wanted -- no g_d, no g_xrow
+// sums or stores, no coordinate atomic; the x part of g_QX_src keeps the zeros of its fill.
+// (A GAM = false form for the last layer -- g_aggm identically zero: no row load, g_m from zero -- was built and measured: 249 registers and no
+// scratch against 256 + 36 bytes, and 28 us SLOWER per launch at cfg4; it is not kept, the zero rows are a fill.  DESIGN.md section 20.)
+template <int MODE, int EA, bool GX = true>
 __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef FE_ISA_CONST   // assembly-only builds of tools/isa_budget_bwd.py: the layer flags as a constant (straight-line code of ONE configuration)
@@ -614,13 +620,13 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
     float acc = 0.f, accx = 0.f;
     auto flush = [&]() {
       A.g_P[(size_t)cur * H + l] = acc;
-      if (l < 3) A.g_xrow[(size_t)cur * 3 + l] = accx;   // lanes 0..2 hold x,y,z (lane 3: pad)
+      if constexpr (GX) { if (l < 3) A.g_xrow[(size_t)cur * 3 + l] = accx; }   // lanes 0..2 hold x,y,z (lane 3: pad)
     };
     // rows without edges inside this wave's range [r0, r1) are zeroed here (no memset ahead of the kernel)
     auto zero_rows = [&](int ra, int rb) {
       for (int r = ra; r < rb; ++r) {
         A.g_P[(size_t)r * H + l] = 0.f;
-        if (l < 3) A.g_xrow[(size_t)r * 3 + l] = 0.f;
+        if constexpr (GX) { if (l < 3) A.g_xrow[(size_t)r * 3 + l] = 0.f; }
       }
     };
     // the indices of a tile are requested one tile ahead (4 registers at EA = 2): of the two dependent round trips at the
@@ -704,7 +710,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
       const float invn = norm_on ? rcp_f(S.nrm + a.eps) : 1.f;
 #pragma unroll
       for (int k = 0; k < 3; ++k) g_d[k] = g_dn[k] * invn + 2.f * g_r * S.d[k];
-      if (valid && !A.g_QXs_atomic) {
+      if (GX && valid && !A.g_QXs_atomic) {   // (GX = false: the atomic scatter is the only form)
         float *qe = A.g_QXe + (size_t)e * QXLD;
         vstore_row(qe, q, g_pre);
         if (q == 0) *reinterpret_cast<f32x4 *>(qe + H) = f32x4{-g_d[0], -g_d[1], -g_d[2], 0.f};
@@ -718,32 +724,34 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
       FE_T(9)   // W2^T product, g_pre, g_d, per-edge stores
       // row-side segment sums: g_P[row] = sum g_pre, g_xrow[row] = sum g_d
       tile_store(pt, j, q, g_pre);
-      if (q == 0) *reinterpret_cast<f32x4 *>(pt + j * TS + H) = f32x4{g_d[0], g_d[1], g_d[2], 0.f};
+      if constexpr (GX) { if (q == 0) *reinterpret_cast<f32x4 *>(pt + j * TS + H) = f32x4{g_d[0], g_d[1], g_d[2], 0.f}; }
       __builtin_amdgcn_wave_barrier();
       float mv[16], xv[16];
 #pragma unroll
       for (int ee = 0; ee < 16; ++ee) {   // all LDS reads up front; the walk below runs on registers
         mv[ee] = pt[ee * TS + l];
-        xv[ee] = pt[ee * TS + H + (l & 3)];
+        if constexpr (GX) xv[ee] = pt[ee * TS + H + (l & 3)];
       }
       const int rowv = S.row;
       if (A.g_QXs_atomic) {   // default (no FASTEGNN_F_DETERMINISTIC): one coalesced 256-byte atomic row per edge ...  (round 6: these atomics are 14 % of the kernel)
         const int colv = S.col;
         char *gb = reinterpret_cast<char *>(A.g_QXs_atomic);   // wave-uniform base + 32-bit lane offsets (tables < 2^30 floats)
-        const unsigned lo = 4u * (unsigned)l;
+        const unsigned lo = 4u * (unsigned)l, qs = 4u * A.gqx.q_ld;
         if (nvalid == 16) {
 #pragma unroll
           for (int ee = 0; ee < 16; ++ee)
-            atomicAdd(reinterpret_cast<float *>(gb + ((unsigned)__builtin_amdgcn_readlane(colv, ee) * (QXLD * 4u) + lo)), mv[ee]);
+            atomicAdd(reinterpret_cast<float *>(gb + ((unsigned)__builtin_amdgcn_readlane(colv, ee) * qs + lo)), mv[ee]);
         } else {
           for (int ee = 0; ee < nvalid; ++ee)
-            atomicAdd(reinterpret_cast<float *>(gb + ((unsigned)__shfl(colv, ee) * (QXLD * 4u) + lo)), pt[ee * TS + l]);
+            atomicAdd(reinterpret_cast<float *>(gb + ((unsigned)__shfl(colv, ee) * qs + lo)), pt[ee * TS + l]);
         }
         // ... and ONE atomic for the tile's coordinate parts: lane l < 3 * nvalid adds component l % 3 of edge l / 3
-        const int ex = min(l / 3, 15), kx = l - 3 * ex;
-        const unsigned cx = (unsigned)__shfl(colv, ex);   // lane ex (q = 0) holds edge ex
-        const float gx = pt[ex * TS + H + (kx & 3)];
-        if (l < 3 * nvalid) atomicAdd(reinterpret_cast<float *>(gb + (cx * (QXLD * 4u) + 4u * (unsigned)(H + kx))), -gx);
+        if constexpr (GX) {
+          const int ex = min(l / 3, 15), kx = l - 3 * ex;
+          const unsigned cx = (unsigned)__shfl(colv, ex);   // lane ex (q = 0) holds edge ex
+          const float gx = pt[ex * TS + H + (kx & 3)];
+          if (l < 3 * nvalid) atomicAdd(reinterpret_cast<float *>(gb + (4u * (A.gqx.x_off + cx * A.gqx.x_ld + (unsigned)kx))), -gx);
+        }
       }
       // row changes inside the tile from one DPP compare + ballot (as in edge_fwd_kernel); the row id is read only at a change
       const int prevrow = __builtin_amdgcn_update_dpp(rowv, rowv, 0x111, 0xf, 0xf, false);   // row_shr:1
@@ -761,7 +769,7 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
           }
           const float gp = mv[ee];
           acc += gp;
-          accx += xv[ee];
+          if constexpr (GX) accx += xv[ee];
           // d edge_mlp.0.weight[:, 2H + k] += g_pre * [radial | edge_attr][k]   (lane = output row);
           // the per-edge scalars come from the owning lane's registers (v_readlane), not from LDS
           accW[0] += gp * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, S.rf), ee));
@@ -808,10 +816,23 @@ __global__ __launch_bounds__(64 * PC_WAVES) void edge_bwd_pc_kernel(EdgeBwdArgs 
   }
 }
 
-int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared) {
+template <bool GX>
+static void launch_edge_bwd_pc(const fastegnn_layer_t *L, dim3 g3, dim3 b3, size_t lds, hipStream_t st, const EdgeBwdArgs &A) {
+  if (L->ea <= 2) {
+    if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_BF16, 2, GX>), g3, b3, lds, st, A);
+    else hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_EDGE_BWD, 2, GX>), g3, b3, lds, st, A);
+  } else {
+    if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_BF16, 7, GX>), g3, b3, lds, st, A);
+    else hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_EDGE_BWD, 7, GX>), g3, b3, lds, st, A);
+  }
+}
+// skip.no_gx (atomic scatter only, checked by
+// fastegnn_layer_backward): no coordinate gradient leaves the stage, g_xrow is not written.
+int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, const BwdSkip &skip) {
   FE_REQUIRE(L->P && L->QX && L->g_aggm && L->g_aggx && L->g_P && L->g_xrow && L->grads && L->wpack,
              "edge_backward: null buffer");
   const bool det = has(L, FASTEGNN_F_DETERMINISTIC);   // store + CSC reduce instead of the atomic scatter
+  FE_REQUIRE(!(det && skip.no_gx), "edge_backward: a null g_x needs the atomic scatter");
   FE_REQUIRE(det ? L->g_QXe != nullptr : L->g_QX_src != nullptr, "edge_backward: g_QXe (deterministic) / g_QX_src null");
   const fastegnn_graph_t &gr = L->graph;
   FE_REQUIRE(!(det && has(L, FASTEGNN_F_GQX_ACCUM)), "edge_backward: FASTEGNN_F_GQX_ACCUM needs the atomic scatter");
@@ -819,7 +840,7 @@ int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared)
     (void)hipMemsetAsync(L->g_QX_src, 0, (size_t)gr.n_src * QXLD * sizeof(float), st);
   if (gr.n_edges == 0 || L->N == 0) {   // nothing to walk (with edges the kernel writes every row of g_P / g_xrow)
     (void)hipMemsetAsync(L->g_P, 0, (size_t)L->N * H * sizeof(float), st);
-    (void)hipMemsetAsync(L->g_xrow, 0, (size_t)L->N * 3 * sizeof(float), st);
+    if (!skip.no_gx) (void)hipMemsetAsync(L->g_xrow, 0, (size_t)L->N * 3 * sizeof(float), st);
     return check_launch("edge_backward(memset)");
   }
   float *const *g = L->grads;
@@ -827,6 +848,7 @@ int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared)
   A.f = make_edge_args(L);
   A.g_aggm = L->g_aggm; A.g_aggx = L->g_aggx; A.g_P = L->g_P; A.g_xrow = L->g_xrow; A.g_QXe = L->g_QXe;
   A.g_QXs_atomic = det ? nullptr : L->g_QX_src;
+  A.gqx = gqx_layout(skip.split_gqx, L->N);
   A.g_ea = L->ea > 0 ? L->g_ea_sorted : nullptr;
   A.ld_e0 = 2 * H + 1 + L->ea;
   A.d_wr = g[FASTEGNN_P_EDGE0_W] + (has(L, FASTEGNN_F_EGNN) ? 0 : 2 * H);   // basic.py:313: radial is column 0
@@ -854,13 +876,8 @@ int edge_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared)
     {
       ProfScope _ps_edge_bwd_kernel(K_EDGE_BWD, st);
       const dim3 g3(grid), b3(64 * PC_WAVES);
-      if (L->ea <= 2) {
-        if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_BF16, 2>), g3, b3, lds, st, A);
-        else hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_EDGE_BWD, 2>), g3, b3, lds, st, A);
-      } else {
-        if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_BF16, 7>), g3, b3, lds, st, A);
-        else hipLaunchKernelGGL((edge_bwd_pc_kernel<GM_EDGE_BWD, 7>), g3, b3, lds, st, A);
-      }
+      if (skip.no_gx) launch_edge_bwd_pc<false>(L, g3, b3, lds, st, A);
+      else launch_edge_bwd_pc<true>(L, g3, b3, lds, st, A);
     }
     if ((rc = check_launch("edge_bwd_pc_kernel"))) return rc;
     return shared ? FASTEGNN_OK : wb.finish();
@@ -970,6 +987,9 @@ struct NodePreBwdArgs {
   int C;
   int flags = 0;
   float act_param = 0.f;
+  GqxLayout gqx = {(unsigned)QXLD, (unsigned)H, (unsigned)QXLD};   // layout of g_QX (kernels.h)
+  int g_h_zero = 0;   // g_h starts from zero instead of from what the virtual stage left there (it left nothing: no gradient for h arrived)
+  // (g_x null: d loss / d x is not wanted -- g_xrow, g_xbar and the x part of g_QX are not read either; g_vel null: not wanted)
 };
 // MODE: GM_X3 / GM_BF16 as in node_pre_fwd_kernel.  LDS: three split images W1AT W1BT V1AT (transposed products only) and the
 // ROW-MAJOR split images of WVEL0 and WG0 (common.h), each serving its product and its transpose: 127 KB instead of the
@@ -999,9 +1019,10 @@ __global__ __launch_bounds__(64 * NODE_PRE_WAVES) void node_pre_bwd_kernel(NodeP
     const int n = tile * 16 + j;
     const bool valid = n < a.N;
     const int nc = valid ? n : a.N - 1;
-    Vec g_h = vload_row(a.g_h + (size_t)nc * H, q);
+    Vec g_h = vzero();
+    if (!a.g_h_zero) g_h = vload_row(a.g_h + (size_t)nc * H, q);   // (wave-uniform)
     gemm_op<MODE>(img3, 0, op(vload_row(a.g_P + (size_t)nc * H, q)), g_h);
-    gemm_op<MODE>(img3, 1, op(vload_row(a.g_QX + (size_t)nc * QXLD, q)), g_h);
+    gemm_op<MODE>(img3, 1, op(vload_row(a.g_QX + (size_t)nc * a.gqx.q_ld, q)), g_h);
     gemm_op<MODE>(img3, 2, op(vload_row(a.g_A + (size_t)nc * H, q)), g_h);
     if (a.has_vel || a.gravity) {
       const Op hv = op(vload_row(a.h + (size_t)nc * H, q));   // one split / rounding feeds both heads
@@ -1040,14 +1061,16 @@ __global__ __launch_bounds__(64 * NODE_PRE_WAVES) void node_pre_bwd_kernel(NodeP
     }
     if (valid) {
       vstore_row(a.g_h + (size_t)n * H, q, g_h);
-      if (q == 0) {
+      if (q == 0 && a.g_x) {
         const int b = a.batch[n];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          a.g_x[(size_t)n * 3 + k] += a.g_xrow[(size_t)n * 3 + k] + a.g_QX[a.gqx.x_off + (size_t)n * a.gqx.x_ld + k] + a.g_xbar[b * 3 + k];
+      }
+      if (q == 0 && a.g_vel) {
         const float sv = a.svel[n];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          a.g_x[(size_t)n * 3 + k] += a.g_xrow[(size_t)n * 3 + k] + a.g_QX[(size_t)n * QXLD + H + k] + a.g_xbar[b * 3 + k];
-          if (a.g_vel) a.g_vel[(size_t)n * 3 + k] += sv * a.g_x_out[(size_t)n * 3 + k];
-        }
+        for (int k = 0; k < 3; ++k) a.g_vel[(size_t)n * 3 + k] += sv * a.g_x_out[(size_t)n * 3 + k];
       }
     }
   }
@@ -1092,9 +1115,10 @@ __global__ __launch_bounds__(64 * NODE_PRE_WAVES) void node_pre_bwd_kernel(NodeP
   }
 }
 
-int node_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared) {
+// skip.dead_rows: the virtual stage has NOT filled g_h with its zero rows; skip.no_gx: g_x is null and stays unwritten
+int node_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, const BwdSkip &skip) {
   FE_REQUIRE(L->h && L->wpack && L->g_P && L->g_QX && L->g_A && L->g_svel && L->g_xrow && L->g_xbar && L->g_x_out &&
-                 L->svel && L->g_h && L->g_x && L->wg_node && L->grads && L->batch,
+                 L->svel && L->g_h && (L->g_x || skip.no_gx) && L->wg_node && L->grads && L->batch,
              "node_pre_backward: null buffer");
   if (L->N == 0) return FASTEGNN_OK;
   const bool grav = has(L, FASTEGNN_F_GRAVITY), rf = has(L, FASTEGNN_F_RF);
@@ -1105,10 +1129,10 @@ int node_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *sha
   float *wg_gzv = wg_np, *wg_gzg = wg_np + (size_t)N * H;
   NodePreBwdArgs a{L->h, L->wpack, L->g_P, L->g_QX, L->g_A, L->g_svel, L->g_sgrav, L->g_xrow, L->g_xbar, L->g_x_out,
                    L->svel, p[FASTEGNN_P_VEL0_B], p[FASTEGNN_P_VEL2_W], p[FASTEGNN_P_GRAV0_B], p[FASTEGNN_P_GRAV2_W],
-                   L->batch, L->g_h, L->g_x, L->g_vel, wg_gzv, wg_gzg,
+                   L->batch, L->g_h, skip.no_gx ? nullptr : L->g_x, L->g_vel, wg_gzv, wg_gzg,
                    g[FASTEGNN_P_VEL2_W], g[FASTEGNN_P_VEL2_B], g[FASTEGNN_P_GRAV2_W], g[FASTEGNN_P_GRAV2_B], N, grav ? 1 : 0,
                    (p[FASTEGNN_P_VEL0_W] && !rf) ? 1 : 0, L->vel, rf ? p[FASTEGNN_P_VEL0_W] : nullptr,
-                   g[FASTEGNN_P_VEL0_W], g[FASTEGNN_P_VEL0_B], L->C, L->flags, L->act_param};
+                   g[FASTEGNN_P_VEL0_W], g[FASTEGNN_P_VEL0_B], L->C, L->flags, L->act_param, gqx_layout(skip.split_gqx, N), skip.dead_rows ? 1 : 0};
   FE_REQUIRE(!rf || (L->vel && p[FASTEGNN_P_VEL0_W] && g[FASTEGNN_P_VEL0_W] && g[FASTEGNN_P_VEL0_B] && g[FASTEGNN_P_VEL2_W] &&
                      g[FASTEGNN_P_VEL2_B]),
              "node_pre_backward: FastRF needs vel and the coord_mlp_vel parameters / gradients");
@@ -1129,7 +1153,7 @@ int node_pre_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *sha
   wb.round = has(L, FASTEGNN_F_BF16);
   const int c0 = has(L, FASTEGNN_F_EGNN) ? 1 : 0;   // EGNN baseline: [radial | h_row | h_col | edge_attr]
   if ((rc = wb.add(L->g_P, H, L->h, H, N, g[FASTEGNN_P_EDGE0_W], ld_e0, c0, 1, g[FASTEGNN_P_EDGE0_B]))) return rc;
-  if ((rc = wb.add(L->g_QX, QXLD, L->h, H, N, g[FASTEGNN_P_EDGE0_W], ld_e0, c0 + H, 1, nullptr))) return rc;
+  if ((rc = wb.add(L->g_QX, skip.split_gqx ? H : QXLD, L->h, H, N, g[FASTEGNN_P_EDGE0_W], ld_e0, c0 + H, 1, nullptr))) return rc;
   // edge_mlp_virtual.0 columns [0,H) <- h (A)   (absent for the EGNN baseline: add() skips a null dW)
   if ((rc = wb.add(L->g_A, H, L->h, H, N, g[FASTEGNN_P_VIRT0_W], ld_v0, 0, 1, nullptr))) return rc;
   if (p[FASTEGNN_P_VEL0_W] && !rf)

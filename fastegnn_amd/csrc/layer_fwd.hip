@@ -310,8 +310,10 @@ int graph_pre_forward(const fastegnn_layer_t *L, hipStream_t st, float *part) {
 // One wave walks an edge-balanced chunk of CSR rows in 16-edge tiles; sums stay in registers
 // until the row changes, so every row is written exactly once (no atomics, deterministic).
 // =====================================================================================
+// AGGM = false (the layer call of a layer without a node update: aggm feeds node_model alone): the message tile is not transposed, its
+// rows are not summed and aggm is not written; aggx is built by the same additions in the same order (bit for bit).
 constexpr int EDGE_FWD_IMG_FLOATS = 2 * IMG3;
-template <int MODE>
+template <int MODE, bool AGGM = true>
 __global__ __launch_bounds__(64 * EDGE_FWD_WAVES) void edge_fwd_kernel(EdgeArgs a, int C) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef FE_ISA_CONST   // assembly-only builds of tools/isa_budget.py: the layer flags as a constant (straight-line code of ONE configuration)
@@ -343,14 +345,14 @@ __global__ __launch_bounds__(64 * EDGE_FWD_WAVES) void edge_fwd_kernel(EdgeArgs 
       int cnt = 0;   // edges of the current row seen so far == its in-degree at flush time (rows never straddle waves)
       auto flush = [&]() {
         const float inv = rcp_f((float)cnt);
-        a.aggm[(size_t)cur * H + l] = acc * (FOLD ? inv * LN2_F : inv);
+        if constexpr (AGGM) a.aggm[(size_t)cur * H + l] = acc * (FOLD ? inv * LN2_F : inv);
         if (l < 3) a.aggx[(size_t)cur * 3 + l] = mean ? accx * inv : accx;
       };
       // rows without edges inside this wave's range get their zeros here (no memset of aggm / aggx ahead of the kernel):
       // the wave owns the rows [r0, r1) and writes each of them exactly once
       auto zero_rows = [&](int ra, int rb) {
         for (int r = ra; r < rb; ++r) {
-          a.aggm[(size_t)r * H + l] = 0.f;
+          if constexpr (AGGM) a.aggm[(size_t)r * H + l] = 0.f;
           if (l < 3) a.aggx[(size_t)r * 3 + l] = 0.f;
         }
       };
@@ -364,7 +366,7 @@ __global__ __launch_bounds__(64 * EDGE_FWD_WAVES) void edge_fwd_kernel(EdgeArgs 
         Vec pre;
         edge_tile_forward<false, MODE>(a, img, vec, cur_i, q, S, pre FE_TA);
         cur_i = nxt_i;
-        tile_store(mt, j, q, S.m);
+        if constexpr (AGGM) tile_store(mt, j, q, S.m);
         if (q == 0) {
           xt[j * 4 + 0] = S.dn[0] * S.s;
           xt[j * 4 + 1] = S.dn[1] * S.s;
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(64 * EDGE_FWD_WAVES) void edge_fwd_kernel(EdgeArgs 
         float mv[16], xv[16];
 #pragma unroll
         for (int ee = 0; ee < 16; ++ee) {
-          mv[ee] = mt[ee * TS + l];
+          if constexpr (AGGM) mv[ee] = mt[ee * TS + l];
           xv[ee] = xt[ee * 4 + (l & 3)];
         }
         const int rowv = S.row;
@@ -398,7 +400,7 @@ __global__ __launch_bounds__(64 * EDGE_FWD_WAVES) void edge_fwd_kernel(EdgeArgs 
               accx = 0.f;
               cnt = 0;
             }
-            acc += mv[ee];
+            if constexpr (AGGM) acc += mv[ee];
             accx += xv[ee];
             ++cnt;
           }
@@ -413,14 +415,14 @@ __global__ __launch_bounds__(64 * EDGE_FWD_WAVES) void edge_fwd_kernel(EdgeArgs 
   FE_TEND()
 }
 
-int edge_forward(const fastegnn_layer_t *L, hipStream_t st) {
+int edge_forward(const fastegnn_layer_t *L, hipStream_t st, bool aggm) {
   FE_REQUIRE(L->P && L->QX && L->aggm && L->aggx && L->wpack, "edge_forward: null buffer");
   FE_REQUIRE(L->ea <= 7, "edge_forward: edge_attr_nf > 7 unsupported");
   FE_REQUIRE(!has(L, FASTEGNN_F_ATTENTION) || (L->params[FASTEGNN_P_ATT_W] && L->params[FASTEGNN_P_ATT_B]),
              "edge_forward: attention params null");
   const fastegnn_graph_t &g = L->graph;
   if (g.n_edges == 0 || L->N == 0) {   // nothing to walk: the aggregates are zero (with edges the kernel writes every row)
-    (void)hipMemsetAsync(L->aggm, 0, (size_t)L->N * H * sizeof(float), st);
+    if (aggm) (void)hipMemsetAsync(L->aggm, 0, (size_t)L->N * H * sizeof(float), st);
     (void)hipMemsetAsync(L->aggx, 0, (size_t)L->N * 3 * sizeof(float), st);
     return check_launch("edge_forward(memset)");
   }
@@ -435,8 +437,13 @@ int edge_forward(const fastegnn_layer_t *L, hipStream_t st) {
   const size_t lds = (EDGE_FWD_IMG_FLOATS + EV_COUNT * H + EDGE_FWD_WAVES * (16 * TS + 64)) * sizeof(float);
   {
     ProfScope _ps_edge_fwd_kernel(K_EDGE_FWD, st);
-    if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL(edge_fwd_kernel<GM_BF16>, dim3(grid), dim3(64 * EDGE_FWD_WAVES), lds, st, a, L->C);
-    else hipLaunchKernelGGL(edge_fwd_kernel<GM_EDGE_FWD>, dim3(grid), dim3(64 * EDGE_FWD_WAVES), lds, st, a, L->C);
+    const dim3 g3(grid), b3(64 * EDGE_FWD_WAVES);
+    if (!aggm) {
+      if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL((edge_fwd_kernel<GM_BF16, false>), g3, b3, lds, st, a, L->C);
+      else hipLaunchKernelGGL((edge_fwd_kernel<GM_EDGE_FWD, false>), g3, b3, lds, st, a, L->C);
+    }
+    else if (has(L, FASTEGNN_F_BF16)) hipLaunchKernelGGL(edge_fwd_kernel<GM_BF16>, g3, b3, lds, st, a, L->C);
+    else hipLaunchKernelGGL(edge_fwd_kernel<GM_EDGE_FWD>, g3, b3, lds, st, a, L->C);
   }
   return check_launch("edge_fwd_kernel");
 }

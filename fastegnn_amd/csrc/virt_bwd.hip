@@ -119,7 +119,8 @@ __global__ __launch_bounds__(64 * VB_NODE_WAVES) void virt_bwd_node_kernel(VirtN
 
 // B4a when no gradient arrives for h (g_h_out == NULL && g_HvT_out == NULL: the forward skipped this layer's node update): g_np = 0, so
 // g_h (the part of this stage) and g_aggm are zero rows; the per-node scalars of the coordinate update are the expressions above.
-// One thread per 16-byte piece of a row.
+// One thread per 16-byte piece of a row.  (The staged entry point; the layer call, whose node_pre stage knows its g_h rows are zero and does
+// not read them, fills g_aggm and runs virt_bwd_node_scalars_kernel below.)
 __global__ __launch_bounds__(256) void virt_bwd_node_skip_kernel(const float *g_x_out, const float *vel, float *g_h, float *g_aggm,
                                                                  float *g_aggx, float *g_svel, float *g_sgrav, int N, int flags,
                                                                  float g0, float g1, float g2) {
@@ -142,6 +143,23 @@ __global__ __launch_bounds__(256) void virt_bwd_node_skip_kernel(const float *g_
     g_svel[n] = sv;
     if (flags & FASTEGNN_F_GRAVITY) g_sgrav[n] = sg;
   }
+}
+// the per-node scalars alone (the same expressions), one thread per node: g_h and g_aggm are not written
+__global__ __launch_bounds__(256) void virt_bwd_node_scalars_kernel(const float *g_x_out, const float *vel, float *g_aggx, float *g_svel,
+                                                                    float *g_sgrav, int N, int flags, float g0, float g1, float g2) {
+  const size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= (size_t)N) return;
+  const float g[3] = {g0, g1, g2};
+  float sv = 0.f, sg = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float gxn = g_x_out[n * 3 + k];
+    g_aggx[n * 3 + k] = gxn;
+    sv += gxn * vel[n * 3 + k];
+    sg += gxn * g[k];
+  }
+  g_svel[n] = sv;
+  if (flags & FASTEGNN_F_GRAVITY) g_sgrav[n] = sg;
 }
 
 // =====================================================================================
@@ -791,7 +809,7 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_pc_kernel(VirtBwd2Args
         }
         VB2_T(10)   // g_pre consumers: g_A through memory, w_vr, pools
       }
-      if (valid && q == 0) {
+      if (A.g_x && valid && q == 0) {   // (g_x null: d loss / d x is not wanted, fastegnn_layer_backward)
         if (grp == 0) {
 #pragma unroll
           for (int k = 0; k < 3; ++k) A.g_x[(size_t)n * 3 + k] = gx[k];
@@ -844,7 +862,7 @@ __global__ __launch_bounds__(256) void virt_bwd_combine_kernel(float *g_A, float
   f32x4 s = reinterpret_cast<const f32x4 *>(g_A + (size_t)n * H)[c4];
   for (int p = 0; p < nparts; ++p) s += reinterpret_cast<const f32x4 *>(gA_part + ((p0 + p) * 16 + row) * H)[c4];
   reinterpret_cast<f32x4 *>(g_A + (size_t)n * H)[c4] = s;
-  if (c4 < 3) {
+  if (g_x && c4 < 3) {
     float sx = g_x[(size_t)n * 3 + c4];
     for (int p = 0; p < nparts; ++p) sx += gx_part[((p0 + p) * 16 + row) * 4 + c4];
     g_x[(size_t)n * 3 + c4] = sx;
@@ -902,6 +920,7 @@ struct VirtCsArgs {
   VirtArgs f;
   const float *g_x_out, *g_poolX, *g_poolV, *g_np;
   float *g_x, *g_A, *g_Bc, *g_Zp;
+  int want_gz = 1;            // GX = false only: 0 = g_Zp is not wanted either (g_Z == NULL)
   float *cons_scratch;        // [grid][5][64*64]: running sums of X, XX, V2 and of the two parities of W (accumulator order)
   float *w_slab;              // [C][grid][64*64] partial sums of dW3c per workgroup, in ACCUMULATOR order (WgAcc32), summed over the blocks
   float *d_wxv2, *d_wxx2, *d_wvr, *d_attw, *d_attb;
@@ -959,7 +978,10 @@ __device__ int g_vbs_timeouts = 0;
 // Gv = 0 -- no g_np row, no W3c^T stage and product, no (g_np, v) contraction: ring A carries (g_ux, g_uX, v) to wave 3 alone, and wave 6
 // is a sixth producer (measured against sitting the launch out: DESIGN.md section 11).  The ticket / flag protocol is NODE = true's:
 // READY still marks "the parity's pool rows are clear".  NODE = true is the kernel as it was.
-template <bool ATT, bool NODE = true>
+// GX = false (g_x == NULL in fastegnn_layer_backward): d loss / d x of the layer inputs is not wanted -- the tile's g_x is neither carried
+// from channel to channel through memory nor stored; without g_Zp as well (want_gz = 0) g_vd, g_vr / vr and the three 16-lane sums of a
+// unit go too.  w_vr's rank-1 sum and every weight gradient stay; the TSEQ hand-on stays (g_A still travels through memory).
+template <bool ATT, bool NODE = true, bool GX = true>
 __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A) {
   constexpr int SM = GM_F16;
   typedef typename OperandOf<SM>::type SOp;
@@ -1317,8 +1339,10 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
         gxn[k] = valid ? A.g_x_out[(size_t)nc * 3 + k] : 0.f;
         xi[k] = a.x[(size_t)nc * 3 + k];
         // the tile's g_x accumulates through memory; the direct path x' = x + ... is counted once, with channel 0
-        gx[k] = c == 0 ? gxn[k] : (valid ? A.g_x[(size_t)nc * 3 + k] : 0.f);
+        if constexpr (GX) gx[k] = c == 0 ? gxn[k] : (valid ? A.g_x[(size_t)nc * 3 + k] : 0.f);
+        else gx[k] = 0.f;
       }
+      const bool want_vd = GX || A.want_gz;   // (wave-uniform)
       float vd[3], gpX[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -1456,30 +1480,36 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
       vadd(ga, g_pre);
       if (valid) vstore_u(A.g_A, offN, ga);
       vb_accum_items(racc + 2 * H, vscale(g_pre, vr), j, q);
-      const float g_vr = vdot(g_pre, vload_vec(vec + VV_WVR * H, q));
-      const float ivr = vr > 0.f ? g_vr * rcp_f(vr) : 0.f;
+      if (want_vd) {
+        const float g_vr = vdot(g_pre, vload_vec(vec + VV_WVR * H, q));
+        const float ivr = vr > 0.f ? g_vr * rcp_f(vr) : 0.f;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        g_vd[k] += ivr * vd[k];
-        gx[k] -= g_vd[k];
+        for (int k = 0; k < 3; ++k) {
+          g_vd[k] += ivr * vd[k];
+          gx[k] -= g_vd[k];
+        }
       }
-      if (valid && q == 0) {
+      if constexpr (GX) {
+        if (valid && q == 0) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) A.g_x[(size_t)n * 3 + k] = gx[k];
+          for (int k = 0; k < 3; ++k) A.g_x[(size_t)n * 3 + k] = gx[k];
+        }
       }
       // pools over the nodes of the tile: g_Bc[b,c,:] += g_pre, g_Zp[b,:,c] += g_vd
       if (pmode < 2) {
-        float pz[3];
+        float pz[3] = {0.f, 0.f, 0.f};
+        if (want_vd) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) pz[k] = jsum((valid && q == 0) ? g_vd[k] : 0.f);
+          for (int k = 0; k < 3; ++k) pz[k] = jsum((valid && q == 0) ? g_vd[k] : 0.f);
+        }
         vb_accum_items(pmode == 0 ? gBc_l + (ph & 1) * H : A.g_Bc + ((size_t)b0 * C + c) * H, g_pre, j, q);
-        if (l < 3) {
+        if (want_vd && l < 3) {
           const float pzl = l == 0 ? pz[0] : (l == 1 ? pz[1] : pz[2]);
           if (pmode == 0) atomicAdd(&gZ_l[(ph & 1) * 4 + l], pzl);
           else atomicAdd(&A.g_Zp[((size_t)b0 * 3 + l) * C + c], pzl);
         }
       } else {
-        if (valid && q == 0) {
+        if (want_vd && valid && q == 0) {
 #pragma unroll
           for (int k = 0; k < 3; ++k) atomicAdd(&A.g_Zp[((size_t)b * 3 + k) * C + c], g_vd[k]);
         }
@@ -1504,7 +1534,7 @@ __global__ __launch_bounds__(64 * VB_WAVES) void virt_bwd_cs_kernel(VirtCsArgs A
         const float pb = gBc_l[(ph & 1) * H + l];
         atomicAdd(&A.g_Bc[((size_t)cur * C + c) * H + l], pb);
         gBc_l[(ph & 1) * H + l] = 0.f;
-        if (l < 3) {
+        if (want_vd && l < 3) {
           atomicAdd(&A.g_Zp[((size_t)cur * 3 + l) * C + c], gZ_l[(ph & 1) * 4 + l]);
           gZ_l[(ph & 1) * 4 + l] = 0.f;
         }
@@ -1582,7 +1612,16 @@ size_t virt_pc_wg_floats(size_t N, size_t C) {
 }
 
 // B4c': the (node, channel) part in the channel-phased form -- one kernel, then the fixed-order reduction of its partial slabs
-static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp, bool node) {
+template <bool GX>
+static void launch_virt_bwd_cs(bool att, bool node, dim3 g3, dim3 b3, size_t lds, hipStream_t st, const VirtCsArgs &A) {
+  if (!node) {
+    if (att) hipLaunchKernelGGL((virt_bwd_cs_kernel<true, false, GX>), g3, b3, lds, st, A);
+    else hipLaunchKernelGGL((virt_bwd_cs_kernel<false, false, GX>), g3, b3, lds, st, A);
+  }
+  else if (att) hipLaunchKernelGGL((virt_bwd_cs_kernel<true, true, GX>), g3, b3, lds, st, A);
+  else hipLaunchKernelGGL((virt_bwd_cs_kernel<false, true, GX>), g3, b3, lds, st, A);
+}
+static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp, bool node, const BwdSkip &skip) {
   const int C = L->C;
   const bool att = has(L, FASTEGNN_F_ATTENTION);
   float *const *g = L->grads;
@@ -1592,7 +1631,8 @@ static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, 
   VirtCsArgs A;
   A.f = make_virt_args(L);
   A.g_x_out = L->g_x_out; A.g_poolX = L->g_poolX; A.g_poolV = L->g_poolV; A.g_np = wg_gnp;
-  A.g_x = L->g_x; A.g_A = L->g_A; A.g_Bc = L->g_Bc; A.g_Zp = L->g_Zp;
+  A.g_x = skip.no_gx ? nullptr : L->g_x; A.g_A = L->g_A; A.g_Bc = L->g_Bc; A.g_Zp = L->g_Zp;
+  A.want_gz = skip.no_gz ? 0 : 1;
   A.cons_scratch = L->wg_virt;
   A.w_slab = L->wg_virt + (size_t)grid * 5 * IMG;
   A.ld_v0 = 2 * H + 1 + C;
@@ -1619,12 +1659,8 @@ static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, 
   {
     ProfScope ps(K_VIRT_BWD, st);
     const dim3 g3(grid), b3(64 * VB_WAVES);
-    if (!node) {
-      if (att) hipLaunchKernelGGL((virt_bwd_cs_kernel<true, false>), g3, b3, lds, st, A);
-      else hipLaunchKernelGGL((virt_bwd_cs_kernel<false, false>), g3, b3, lds, st, A);
-    }
-    else if (att) hipLaunchKernelGGL((virt_bwd_cs_kernel<true>), g3, b3, lds, st, A);
-    else hipLaunchKernelGGL((virt_bwd_cs_kernel<false>), g3, b3, lds, st, A);
+    if (skip.no_gx) launch_virt_bwd_cs<false>(att, node, g3, b3, lds, st, A);
+    else launch_virt_bwd_cs<true>(att, node, g3, b3, lds, st, A);
   }
   if ((rc = check_launch("virt_bwd_cs_kernel"))) return rc;
   if (!node) return bb.finish();   // no (g_np, v) slabs: node_mlp.0 has no gradient
@@ -1637,8 +1673,9 @@ static int virt_backward_channels_cs(const fastegnn_layer_t *L, hipStream_t st, 
 // B4b + B4c: the (node, channel) part -- Gv, then the producer / consumer kernel and its weight gradients
 // node = false (no gradient arrives for h / Hv): the phased form runs its NODE = false instantiation; the tile-major form (small inputs,
 // bf16 operands) takes Gv = 0 like the FastRF wiring does and queues no node_mlp.0 job
-static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp, bool node) {
-  if (virt_cs_applies(L->N, L->C, L->flags)) return virt_backward_channels_cs(L, st, wg_gnp, node);
+static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, float *wg_gnp, bool node, const BwdSkip &skip) {
+  if (virt_cs_applies(L->N, L->C, L->flags)) return virt_backward_channels_cs(L, st, wg_gnp, node, skip);
+  float *const g_x = skip.no_gx ? nullptr : L->g_x;   // (null: the kernels below write no g_x, wave-uniform checks)
   const int N = L->N, C = L->C, ntiles = cdiv(N, 16);
   const bool bf = has(L, FASTEGNN_F_BF16), att = has(L, FASTEGNN_F_ATTENTION), rf = has(L, FASTEGNN_F_RF);
   float *const *g = L->grads;
@@ -1670,7 +1707,7 @@ static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, flo
   VirtBwd2Args A;
   A.f = make_virt_args(L);
   A.g_x_out = L->g_x_out; A.g_poolX = L->g_poolX; A.Gv = Gv;
-  A.g_x = L->g_x; A.g_A = L->g_A; A.g_Bc = L->g_Bc; A.g_Zp = L->g_Zp;
+  A.g_x = g_x; A.g_A = L->g_A; A.g_Bc = L->g_Bc; A.g_Zp = L->g_Zp;
   A.gA_part = gA_part; A.gx_part = gx_part; A.wg_v = wg_v; A.cstride = cstride;
   A.cons_scratch = gx_part + (size_t)256 * VB_FINE_TILES * (NGF - 1) * 16 * 4;
   A.ld_v0 = 2 * H + 1 + C;
@@ -1704,7 +1741,7 @@ static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, flo
   }
   if ((rc = check_launch("virt_bwd_pc_kernel"))) return rc;
   if (NGF > 1) {
-    hipLaunchKernelGGL(virt_bwd_combine_kernel, dim3(grid * VB_FINE_TILES), dim3(256), 0, st, L->g_A, L->g_x, gA_part, gx_part, N, NGF - 1, grid);
+    hipLaunchKernelGGL(virt_bwd_combine_kernel, dim3(grid * VB_FINE_TILES), dim3(256), 0, st, L->g_A, g_x, gA_part, gx_part, N, NGF - 1, grid);
     if ((rc = check_launch("virt_bwd_combine_kernel"))) return rc;
   }
   // node_mlp.0 block of channel c: (g_np, v[:, c]) -- one batch slice per channel
@@ -1717,7 +1754,7 @@ static int virt_backward_channels(const fastegnn_layer_t *L, hipStream_t st, flo
 
 // One form for the three wirings: FastEGNN; FastRF (FASTEGNN_F_RF: no node_model -- B4a passes g_h through, Gv = 0, no
 // node_mlp jobs); the EGNN baseline (FASTEGNN_F_EGNN, C = 0: B4a and the node_mlp jobs only).
-int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, bool acc_zeroed) {
+int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared, bool acc_zeroed, const BwdSkip &skip) {
   const bool egnn = has(L, FASTEGNN_F_EGNN), rf = has(L, FASTEGNN_F_RF);
   // g_h_out == NULL && g_HvT_out == NULL (FastEGNN wiring): no gradient arrives for h / Hv, and the forward of this layer skipped the
   // node update -- npre and g_poolV are not read and may be null as well (include/fastegnn_hip.h)
@@ -1725,7 +1762,7 @@ int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared,
   FE_REQUIRE(node || !L->g_HvT_out, "virt_backward: g_h_out is null and g_HvT_out is not (both null: no gradient for h / Hv; otherwise neither)");
   FE_REQUIRE(L->h && L->A && L->x && L->vel && L->aggm && (!node || L->npre) && L->batch && L->wpack && (!egnn || L->aggx),
              "virt_backward: null saved buffer");
-  FE_REQUIRE((!node || L->g_h_out) && L->g_x_out && L->g_h && L->g_x && L->g_A && L->g_aggm && L->g_aggx && L->g_svel && L->wg_node &&
+  FE_REQUIRE((!node || L->g_h_out) && L->g_x_out && L->g_h && (L->g_x || skip.no_gx) && L->g_A && L->g_aggm && L->g_aggx && L->g_svel && L->wg_node &&
                  L->grads && L->wg_slab,
              "virt_backward: null gradient buffer");
   FE_REQUIRE(egnn ? L->C == 0
@@ -1746,8 +1783,14 @@ int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared,
   int rc;
   if (!node) {   // B4a without the node_mlp adjoint
     ProfScope ps(K_VIRT_BWD_NODE, st);
-    hipLaunchKernelGGL(virt_bwd_node_skip_kernel, dim3(cdiv((long)N * (H / 4), 256)), dim3(256), 0, st, L->g_x_out, L->vel, L->g_h, L->g_aggm,
-                       L->g_aggx, L->g_svel, L->g_sgrav, N, L->flags, L->gravity[0], L->gravity[1], L->gravity[2]);
+    if (!skip.dead_rows)
+      hipLaunchKernelGGL(virt_bwd_node_skip_kernel, dim3(cdiv((long)N * (H / 4), 256)), dim3(256), 0, st, L->g_x_out, L->vel, L->g_h, L->g_aggm,
+                         L->g_aggx, L->g_svel, L->g_sgrav, N, L->flags, L->gravity[0], L->gravity[1], L->gravity[2]);
+    else {
+      (void)hipMemsetAsync(L->g_aggm, 0, (size_t)N * H * sizeof(float), st);   // (the edge stage reads the zero rows)
+      hipLaunchKernelGGL(virt_bwd_node_scalars_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, L->g_x_out, L->vel, L->g_aggx, L->g_svel,
+                         L->g_sgrav, N, L->flags, L->gravity[0], L->gravity[1], L->gravity[2]);
+    }
   } else {   // B4a
     VirtNodeArgs a{L->g_h_out, L->npre, L->g_x_out, L->vel, L->aggx, L->wpack, wg_t3, wg_gnp, L->g_h, L->g_aggm, L->g_aggx,
                    L->g_svel, L->g_sgrav, N, L->flags, C, {L->gravity[0], L->gravity[1], L->gravity[2]}, L->act_param};
@@ -1762,7 +1805,7 @@ int virt_backward(const fastegnn_layer_t *L, hipStream_t st, WgradBatch *shared,
     (void)hipMemcpyAsync(L->g_x, L->g_x_out, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
     (void)hipMemsetAsync(L->g_A, 0, (size_t)N * H * sizeof(float), st);
     if ((rc = check_launch("virt_backward(C = 0)"))) return rc;
-  } else if ((rc = virt_backward_channels(L, st, wg_gnp, node))) {
+  } else if ((rc = virt_backward_channels(L, st, wg_gnp, node, skip))) {
     return rc;
   }
   if (rf || !node) return FASTEGNN_OK;   // no node_mlp (FastRF) / no gradient for it

@@ -597,6 +597,20 @@ def _skip_last_node_update(spec) -> bool:
     return not (spec.flags & K.F_RF) and os.environ.get("FASTEGNN_KEEP_DEAD_NODE_UPDATE", "0") in ("", "0")
 
 
+def _keep_dead_edge_work() -> bool:
+    """FASTEGNN_KEEP_DEAD_EDGE_WORK=1 is a DIAGNOSTIC (read per call, here and by the library's layer calls): every gradient pointer is passed and
+    the library runs the unspecialised stages -- the baseline that the skipped edge-stage work of the first and last layer is
+    tested and measured against."""
+    return os.environ.get("FASTEGNN_KEEP_DEAD_EDGE_WORK", "0") not in ("", "0")
+
+
+def _aligned_empty(n_floats: int, align_bytes: int, **kw):
+    """n_floats fp32 elements whose address is a multiple of align_bytes"""
+    buf = torch.empty(n_floats + align_bytes // 4, **kw)
+    off = (-buf.data_ptr() % align_bytes) // 4
+    return buf[off:off + n_floats]
+
+
 # ------------------------------------------------------------------------------------------
 # forward-only execution (DESIGN.md section 16): a forward that can have no backward runs on ONE set of stage buffers
 # ------------------------------------------------------------------------------------------
@@ -817,7 +831,12 @@ class _FastEGNNFunction(torch.autograd.Function):
         g_x = (g_loc if g_loc is not None else torch.zeros(N, 3, **f32)).contiguous().float()
         g_Z = (g_vloc if g_vloc is not None else torch.zeros(B, 3, Cn, **f32)).contiguous().float()
         g_HvT = None if skip_last else torch.zeros(B, Cn, H, **f32)
-        g_vel = torch.zeros(N, 3, **f32)
+        # input gradients nobody asked for are not computed (null pointers: include/fastegnn_hip.h) -- g_vel in every layer, g_x / g_Z of the
+        # layer inputs in layer 0, where they are d loss / d node_loc and d loss / d loc_mean; the null g_x / g_Z convention needs the
+        # atomic scatter
+        keep = _keep_dead_edge_work() or bool(spec.flags & (K.F_DETERMINISTIC | K.F_RF))
+        want_x, want_vel, want_Z = (ctx.needs_input_grad[i] or keep for i in (7, 8, 9))
+        g_vel = torch.zeros(N, 3, **f32) if want_vel else None
         want_ea = ctx.needs_input_grad[4] and ea_sorted is not None and E > 0
         want_na = ctx.needs_input_grad[5] and node_attr is not None
         g_ea_sorted = torch.zeros(E, spec.ea, **f32) if want_ea else None
@@ -825,22 +844,27 @@ class _FastEGNNFunction(torch.autograd.Function):
         scratch = _carve(dev, dict(
             g_poolV=(B, Cn, H), g_poolX=(B, 3, Cn), g_Bc=(B, Cn, H), g_Zp=(B, 3, Cn), g_xbar=(B, 4),
             g_A=(N, H), g_P=(N, H), g_aggm=(N, H), g_aggx=(N, 3), g_svel=(N,), g_sgrav=(N,),
-            g_QXe=(max(E, 1) if spec.flags & K.F_DETERMINISTIC else 1, K.QX_LD), g_QX_src=(N, K.QX_LD), g_xrow=(N, 3),
+            g_QXe=(max(E, 1) if spec.flags & K.F_DETERMINISTIC else 1, K.QX_LD), g_xrow=(N, 3),
             wg_edge=(lib.fastegnn_wg_edge_floats(E),), wg_virt=(lib.fastegnn_wg_virt_floats_for(N, Cn, spec.flags),),
             wg_node=(lib.fastegnn_wg_node_floats(N, B, Cn),),
             wg_slab=(lib.fastegnn_wg_slab_floats(),)))
+        # an allocation of its own on a 256-byte boundary: the library then scatters into 256-byte rows that start on a cache line
+        scratch["g_QX_src"] = _aligned_empty(N * K.QX_LD, 256, **f32).view(N, K.QX_LD)
         for i in reversed(range(spec.n_layers)):
             b = saved[i]
             ptab = _PtrTable([params[s] if s is not None else None for s in spec.layer_slots[i]])
             gtab = _PtrTable([grads[s] if s is not None else None for s in spec.layer_slots[i]])
             L = _new_layer(spec, N, B, graph)
-            out = dict(g_h=torch.empty(N, H, **f32), g_x=torch.empty(N, 3, **f32),
-                       g_Z=torch.empty(B, 3, Cn, **f32), g_HvT=torch.empty(B, Cn, H, **f32))
+            out = dict(g_h=torch.empty(N, H, **f32), g_HvT=torch.empty(B, Cn, H, **f32))
+            if i > 0 or want_x:
+                out["g_x"] = torch.empty(N, 3, **f32)
+            if i > 0 or want_Z:
+                out["g_Z"] = torch.empty(B, 3, Cn, **f32)
             up = dict(g_x_out=g_x, g_Z_out=g_Z)
             if g_h is not None:
                 up.update(g_h_out=g_h, g_HvT_out=g_HvT)
             _fill(L, batch=batch32, gptr=gptr, vel=node_vel, params=ptab.addr(), grads=gtab.addr(),
-                  g_vel=g_vel, **up, **b, **out, **scratch)
+                  **({} if g_vel is None else dict(g_vel=g_vel)), **up, **b, **out, **scratch)
             L.QX_src = b["QX"].data_ptr()
             L.g_QX = scratch["g_QX_src"].data_ptr()
             if ea_sorted is not None:
@@ -852,7 +876,7 @@ class _FastEGNNFunction(torch.autograd.Function):
             if g_na is not None:
                 L.g_node_attr = g_na.data_ptr()
             K.check(lib.fastegnn_layer_backward(C.byref(L), st), f"fastegnn_layer_backward[{i}]")
-            g_h, g_x, g_Z, g_HvT = out["g_h"], out["g_x"], out["g_Z"], out["g_HvT"]
+            g_h, g_x, g_Z, g_HvT = out["g_h"], out.get("g_x"), out.get("g_Z"), out["g_HvT"]
             saved[i] = None
         K.check(lib.fastegnn_virtual_init_backward(K.ptr(g_HvT), B, Cn, K.ptr(grads[0]), st),
                 "fastegnn_virtual_init_backward")
@@ -873,6 +897,7 @@ class _FastEGNNFunction(torch.autograd.Function):
         for s_, suffix in zip(spec.layer_slots[last], K.PARAM_SLOTS):
             if s_ is not None and suffix.startswith(("node_mlp.", "node_mlp_virtual.")) and not (spec.flags & K.F_RF):
                 grads[s_] = None
+        g_x, g_vel, g_Z = (g if ctx.needs_input_grad[i] else None for i, g in ((7, g_x), (8, g_vel), (9, g_Z)))
         return (None, None, None, None, g_ea, g_na, g_nf, g_x, g_vel, g_Z, *grads)
 
 

@@ -213,7 +213,14 @@ typedef struct {
    * node_mlp.* and node_mlp_virtual.* are left untouched, npre, poolV and g_poolV are not read and may be null; g_h, g_x, g_Z, g_HvT
    * and every other gradient are what a zero g_h_out / g_HvT_out gives.  Exactly one of the two null is FASTEGNN_E_INVALID. */
   const float *g_h_out, *g_x_out, *g_Z_out, *g_HvT_out;
-  /* backward outputs: d loss / d layer inputs */
+  /* backward outputs: d loss / d layer inputs.
+   * fastegnn_layer_backward only, FastEGNN wiring with the atomic scatter (no FASTEGNN_F_DETERMINISTIC / _RF / _EGNN: FASTEGNN_E_INVALID before
+   * any launch there), as for g_vel / g_ea_sorted / g_node_attr below -- null means "not wanted":
+   *   g_x == NULL  d loss / d x is not wanted (the first layer of a model whose positions need no gradient): the edge stage forms no
+   *                coordinate adjoint (no g_xrow sums, no coordinate atomic), the virtual stage carries no g_x from channel to channel, the
+   *                graph and node_pre stages write neither g_x nor g_xbar.  g_xrow and g_xbar must still be valid scratch; they are not touched.
+   *   g_Z == NULL  d loss / d Z is not wanted: the graph stages write no g_Z; with g_x null as well the virtual stage does not form g_Zp.
+   * Every other gradient is what it is with the pointers set.  The staged entry points require both, as before ("null buffer"). */
   float *g_h, *g_x, *g_Z, *g_HvT;
   float *g_vel;            /* [N,3] accumulated (+=), may be null */
   float *g_ea_sorted;      /* [E,ea] d loss / d edge_attr in sorted-edge order, accumulated (+=) over the layers; null: not wanted */
@@ -229,7 +236,10 @@ typedef struct {
   float *g_aggx;              /* [N,3] */
   float *g_svel, *g_sgrav;    /* [N] */
   float *g_QXe;               /* [E,68]  per-edge d/d(Q|x) of the col side */
-  float *g_QX_src;            /* [n_src,68] col-keyed sums (sharded: reduce-scattered) */
+  float *g_QX_src;            /* [n_src,68] col-keyed sums (sharded: reduce-scattered).  fastegnn_layer_backward with g_QX == g_QX_src,
+                               * n_src == N, the atomic scatter, no FASTEGNN_F_GQX_ACCUM and a base that is a multiple of 128 bytes uses the
+                               * same N * 68 floats as a Q block [N,64] followed by an x block [N,4]: the 256-byte atomic row of an edge then
+                               * lies in two 128-byte lines instead of three.  Scratch either way: nothing outside the call reads it. */
   float *g_QX;                /* [N,68]  this rank's slice of g_QX_src (== g_QX_src on one GPU) */
   float *g_xrow;              /* [N,3]   row-side d/dx of the edge stage */
   float *wg_edge;             /* [fastegnn_wg_edge_floats(E)] weight-gradient operands of the edge stage (none when the
@@ -353,6 +363,18 @@ int fastegnn_zero_if_flagged(float *buf, int64_t n, const int32_t *flag, void *s
  * launch then finished with wrong results instead of hanging the device); < 0: the query failed.  SYNCHRONISES the device: for tests and
  * post-mortems, not for the step.  ABI revision 107. */
 int fastegnn_spin_timeouts(int reset);
+/* Which specialised path did the layer calls take?  out[FASTEGNN_PATH_COUNT] receives the number of fastegnn_layer_forward /
+ * fastegnn_layer_backward calls since the last reset that returned FASTEGNN_OK after taking
+ *   FASTEGNN_PATH_NO_AGGM     forward, h_out == NULL && HvT_out == NULL: the edge stage did not build aggm (it feeds node_model alone; the
+ *                             buffer itself stays non-null: it parks the per-block coordinate sums ahead of the edge stage)
+ *   FASTEGNN_PATH_ZERO_GAGGM  backward, g_h_out == NULL && g_HvT_out == NULL: the zero rows of this layer's part of g_h were neither filled
+ *                             nor read, and g_aggm was a plain fill (the staged entry points fill and read both as before)
+ *   FASTEGNN_PATH_NO_GX       backward, g_x == NULL: no coordinate gradient of the layer inputs was formed (fastegnn_layer_t.g_x)
+ *   FASTEGNN_PATH_SPLIT_GQX   backward: g_QX_src was used as a Q block [N,64] followed by an x block [N,4] (see g_QX_src)
+ * reset != 0 clears the counts.  Host-side counters, no device work, not thread-safe: for tests.  FASTEGNN_KEEP_DEAD_EDGE_WORK=1 in the
+ * environment (a DIAGNOSTIC, read per call) makes the layer calls run the unspecialised stages.  An additive export (revision 108). */
+enum { FASTEGNN_PATH_NO_AGGM = 0, FASTEGNN_PATH_ZERO_GAGGM = 1, FASTEGNN_PATH_NO_GX = 2, FASTEGNN_PATH_SPLIT_GQX = 3, FASTEGNN_PATH_COUNT = 4 };
+int fastegnn_path_counts(int64_t *out, int32_t reset);
 /* batch int64 [N] (ascending) -> batch int32 [N], gptr int32 [B+1] */
 int fastegnn_build_batch(const int64_t *batch64, int32_t N, int32_t B, int32_t *batch, int32_t *gptr,
                          void *stream);
