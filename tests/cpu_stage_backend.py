@@ -141,6 +141,8 @@ class CpuOracleBackend:
     def _stage(self, name, N, B, graph, t, params, grads, flags):
         from fastegnn_amd._lib import F_GQX_ACCUM
         cfg, R = self.cfg, F.R
+        wiring = F.wiring_of(cfg)
+        act, dact = F.act_pair(cfg)
         dt = self._dtype(t)
         w, _ = self._w(params)
         G = self._G(grads, params) if grads is not None else None
@@ -150,7 +152,7 @@ class CpuOracleBackend:
         if name == "pack_weights":
             return
         if name == "node_pre_forward":
-            P, Q, A, svel, sgrav = F.node_pre_fwd(w, cfg, t["h"])
+            P, Q, A, svel, sgrav = F.node_pre_fwd(w, cfg, t["h"], t.get("vel"))
             t["P"].copy_(P); t["A"].copy_(A); t["svel"].copy_(svel)
             if sgrav is not None:
                 t["sgrav"].copy_(sgrav)
@@ -170,6 +172,12 @@ class CpuOracleBackend:
         elif name == "virt_forward":
             # h_out and HvT_out both absent (include/fastegnn_hip.h): the node update is not wanted -- npre / poolV are not written
             node = _present(t, "h_out")
+            if wiring != "fastegnn" and not node:
+                raise ValueError("virt_forward: a null h_out under the rf / egnn wiring")
+            if wiring == "egnn":
+                h_new, x_new = F.egnn_node_fwd(w, cfg, t["h"], t["x"], t["vel"], t["aggm"], t["aggx"], t["svel"])
+                t["h_out"].copy_(h_new); t["x_out"].copy_(x_new)
+                return
             if not node and _present(t, "HvT_out"):
                 raise ValueError("virt_forward: h_out is null and HvT_out is not")
             h_new, x_new, poolV, poolX = F.virt_fwd(w, cfg, t["h"], t["A"], t["Bc"], t["x"], t["vel"], t["Z"], batch,
@@ -181,17 +189,23 @@ class CpuOracleBackend:
         elif name == "graph_post_forward":
             inv = (1.0 / cnt).view(-1, 1, 1)
             t["Z_out"].copy_(t["Z"] + t["poolX"] * inv)
+            if wiring == "rf":                   # the virtual features pass through
+                t["HvT_out"].copy_(t["HvT"])
+                return
             if not _present(t, "HvT_out"):
                 if _present(t, "h_out"):
                     raise ValueError("graph_post_forward: HvT_out is null and h_out is not")
                 return
             z5 = R(t["HvT"]) @ R(w.W5a).T + R(t["poolV"] * inv) @ R(w.W5b).T + w.b5
-            out = R(F.silu(z5)) @ R(w.W6).T + w.b6
+            out = R(act(z5)) @ R(w.W6).T + w.b6
             t["HvT_out"].copy_(t["HvT"] + out if cfg.residual else out)
         elif name == "graph_post_backward":
             inv = (1.0 / cnt).view(-1, 1, 1)
             t["g_poolX"].copy_(t["g_Z_out"] * inv)
             t["g_Z"].copy_(t["g_Z_out"])
+            if wiring == "rf":                   # the adjoint of the identity; g_poolV is zeroed (nothing pools v)
+                t["g_HvT"].copy_(t["g_HvT_out"]); t["g_poolV"].zero_()
+                return
             if not _present(t, "g_HvT_out"):     # no gradient arrives for Hv: node_mlp_virtual's adjoint is not run
                 if _present(t, "g_h_out"):
                     raise ValueError("graph_post_backward: g_HvT_out is null and g_h_out is not")
@@ -199,11 +213,11 @@ class CpuOracleBackend:
                 return
             pm = t["poolV"] * inv
             z5 = R(t["HvT"]) @ R(w.W5a).T + R(pm) @ R(w.W5b).T + w.b5
-            u = F.silu(z5)
+            u = act(z5)
             g_out = t["g_HvT_out"]
             G["L.node_mlp_virtual.2.bias"] += g_out.sum((0, 1))
             G["L.node_mlp_virtual.2.weight"] += torch.einsum("bco,bch->oh", R(g_out), R(u))
-            g_z5 = (R(g_out) @ R(w.W6)) * F.dsilu(z5)
+            g_z5 = (R(g_out) @ R(w.W6)) * dact(z5)
             G["L.node_mlp_virtual.0.bias"] += g_z5.sum((0, 1))
             G["L.node_mlp_virtual.0.weight"][:, :H] += torch.einsum("bco,bch->oh", R(g_z5), R(t["HvT"]))
             G["L.node_mlp_virtual.0.weight"][:, H:] += torch.einsum("bco,bch->oh", R(g_z5), R(pm))
@@ -211,6 +225,13 @@ class CpuOracleBackend:
             t["g_poolV"].copy_((R(g_z5) @ R(w.W5b)) * inv)
         elif name == "virt_backward":
             node = _present(t, "g_h_out")
+            if wiring != "fastegnn" and not node:
+                raise ValueError("virt_backward: a null g_h_out under the rf / egnn wiring")
+            if wiring == "egnn":
+                r = F.egnn_node_bwd(w, cfg, G, "L", t["h"], t["vel"], t["aggm"], t["aggx"], t["g_h_out"], t["g_x_out"])
+                for k, v in r.items():
+                    t[k].copy_(v)
+                return
             if not node and _present(t, "g_HvT_out"):
                 raise ValueError("virt_backward: g_h_out is null and g_HvT_out is not")
             Gv = G
@@ -262,7 +283,7 @@ class CpuOracleBackend:
         elif name == "node_pre_backward":
             gq = t["g_QX"]
             g_h = F.node_pre_bwd(w, cfg, G, "L", t["h"], t["g_P"], gq[:N, :H], t["g_A"], t["g_svel"],
-                                 t["g_sgrav"] if grav is not None else None)
+                                 t["g_sgrav"] if grav is not None else None, t.get("vel"))
             t["g_h"] += g_h
             t["g_x"] += t["g_xrow"] + gq[:N, H:H + 3] + t["g_xbar"][batch, :3]
             if _present(t, "g_vel"):

@@ -21,6 +21,14 @@ fp64: exact to 1e-16), so the HIP kernels and the fp64 truth see the same operan
 node_pre_forward are divided by the scale before they are compared.  Gradients are with respect to the true P / Q in
 every build.
 
+Wirings and activations.  make_case takes a wiring -- ("fastegnn",), ("rf",) or ("egnn", with_v, norm) -- and an activation
+(Config.act, Config.act_param); the case then carries an oracle.factored.StageConfig, the parameter slots of that wiring's oracle,
+and HipRunner builds fastegnn_amd.FastRF / fastegnn_amd.EGNN for its flags.  The EGNN wiring has six stages, one graph (B = 1, a zero
+batch) and no virtual buffers; its cases carry an aggx that engages the +-100 clamp and, under norm, pairs below the normalisation's
+epsilon.  Without the velocity head (with_v=False) nothing changes in what a stage writes: node_pre_forward stores a zero svel,
+virt_backward writes g_svel = <g_x_out, vel> and node_pre_backward adds svel x g_x_out to g_vel without reading g_svel -- every one
+of them is compared.  The tables of these cases are at the end of the file; MATRIX and stage_cases are what they were.
+
 No GPU import at module level: the CPU tests use everything but HipRunner."""
 from __future__ import annotations
 
@@ -46,6 +54,7 @@ GRAVITY = (0.25, -1.0, 0.5)    # not an axis: a swapped component shows
 FORWARD = ("node_pre_forward", "graph_xsum", "graph_pre_forward", "edge_forward", "virt_forward", "graph_post_forward")
 BACKWARD = ("graph_post_backward", "virt_backward", "graph_pre_backward", "edge_backward", "node_pre_backward")
 STAGES = FORWARD + BACKWARD
+EGNN_STAGES = ("node_pre_forward", "edge_forward", "virt_forward", "virt_backward", "edge_backward", "node_pre_backward")
 EDGE_STAGES = ("edge_forward", "edge_backward")
 GRAPH_LEVEL = ("graph_xsum", "graph_pre_forward", "graph_post_forward", "graph_post_backward", "graph_pre_backward")
 
@@ -54,8 +63,21 @@ PER_GRAPH = ("Bc", "poolV", "poolX", "Z_out", "HvT_out", "g_Bc", "g_Zp", "g_HvT"
 MIXED_QX = ("QX", "g_QX_src", "g_QXe")
 
 
-def config(C: int, ea: int, na: int, flags: Tuple[str, ...]) -> R.Config:
+FASTEGNN_WIRING, SILU = ("fastegnn",), ("silu", 0.0)
+
+
+def config(C: int, ea: int, na: int, flags: Tuple[str, ...], wiring: tuple = FASTEGNN_WIRING, act: tuple = SILU) -> R.Config:
+    """wiring: ("fastegnn",) | ("rf",) | ("egnn", with_v, norm); act: (Config.act, Config.act_param)"""
     assert set(flags) <= set(FLAGS), flags
+    if wiring != FASTEGNN_WIRING or act != SILU:
+        from oracle.factored import StageConfig
+        egnn = wiring[0] == "egnn"
+        assert wiring[0] in ("fastegnn", "rf") or (egnn and C == 0 and na == 0 and not flags), (wiring, C, na, flags)
+        return StageConfig(node_feat_nf=1, node_attr_nf=na, edge_attr_nf=ea, hidden_nf=H, virtual_channels=C, n_layers=1,
+                           residual="noresidual" not in flags and not egnn, attention="attention" in flags,
+                           normalize="normalize" in flags, tanh="tanh" in flags, gravity=list(GRAVITY) if "gravity" in flags else None,
+                           coords_agg="sum" if "coords_sum" in flags else "mean", bf16="bf16" in flags, act=act[0], act_param=act[1],
+                           wiring=wiring[0], with_v=bool(wiring[1]) if egnn else True, norm=bool(wiring[2]) if egnn else False)
     return R.Config(node_feat_nf=1, node_attr_nf=na, edge_attr_nf=ea, hidden_nf=H, virtual_channels=C, n_layers=1,
                     residual="noresidual" not in flags, attention="attention" in flags, normalize="normalize" in flags,
                     tanh="tanh" in flags, gravity=list(GRAVITY) if "gravity" in flags else None,
@@ -80,6 +102,8 @@ class Case:
     batch: torch.Tensor                       # int64 [N]
     t: Dict[str, torch.Tensor]                # every other buffer, fp64 tensors holding fp32 values
     key: tuple = ()                           # the arguments of make_case
+    wiring: tuple = ("fastegnn",)
+    act: tuple = ("silu", 0.0)
 
 
 # --------------------------------------------------------------------------
@@ -140,12 +164,80 @@ def _edges(kind: str, sizes, n_src: int, row_begin: int, g: torch.Generator) -> 
 # --------------------------------------------------------------------------
 # cases
 # --------------------------------------------------------------------------
+def _layer_params(cfg, wiring, seed):
+    """one layer's parameters under the FASTEGNN_P_* slot names, from the parameter set of the wiring's oracle: oracle.fastegnn_ref's
+    (init_params), oracle.fastrf_ref's (the same without node_mlp / node_mlp_virtual, coord_mlp_vel.0.weight [H,1]), oracle.egnn_ref's
+    (state_dict keys of models/basic.py, mapped to slots as fastegnn_amd.egnn does)"""
+    dt = torch.float64
+    if wiring[0] == "egnn":
+        from fastegnn_amd.egnn import _SLOT_OF
+        g = torch.Generator().manual_seed(seed)
+        q = {}
+        for name, (o, i) in {"edge_message_net.scalar_net.mlp.0": (H, 1 + 2 * H + cfg.edge_attr_nf), "edge_message_net.scalar_net.mlp.2": (H, H),
+                             "coord_net.mlp.0": (H, H), "coord_net.mlp.2": (1, H), "node_net.mlp.0": (H, 2 * H), "node_net.mlp.2": (H, H),
+                             **({"node_v_net.mlp.0": (H, H), "node_v_net.mlp.2": (1, H)} if cfg.with_v else {})}.items():
+            lin = R._linear(g, o, i, dtype=dt)
+            if name == "coord_net.mlp.2":                  # an O(1) head, as coord_gain = 1.0 below
+                lin["weight"] = R._xavier(g, o, i, 1.0, dtype=dt)["weight"]
+            q[name + ".weight"], q[name + ".bias"] = lin["weight"], lin["bias"]
+        return {"gcl_0." + slot: q[key].float().double() for slot, key in _SLOT_OF.items() if key in q}
+    # O(1) heads (coord_gain 1.0, not the 1e-3 of a fresh model): no output hides behind a small weight
+    p = {k: v.float().double() for k, v in R.init_params(cfg, seed=seed, coord_gain=1.0, dtype=dt).items()}
+    if wiring[0] == "rf":
+        p = {k: v for k, v in p.items() if ".node_mlp" not in k}
+        p["gcl_0.coord_mlp_vel.0.weight"] = R._linear(torch.Generator().manual_seed(7700 + seed), H, 1, dtype=dt)["weight"].float().double()
+    return p
+
+
+def _ulps(v, k):
+    """v + k units in the last place of each fp32 component of v (exact in fp32; v != 0)"""
+    return v + k * torch.exp2(torch.floor(torch.log2(v.abs())) - 23)
+
+
+def _egnn_operand_edges(cfg, t, ei, n_src, row_begin, g):
+    """the two operand edges of the EGNN wiring a random draw does not produce (after the draw, in place)
+    clamp engaged: aggx x 100 (about a third of its components beyond +-100), eight components exactly on the gate's boundary;
+    norm below its epsilon: eight connected pairs whose coordinates differ by 1..4 ulps per component (r < 1e-12, r x 1e12 a live
+    feature with derivative 1e12) and four that coincide (r = 0) -- fewer of each on a graph too small for twelve disjoint pairs.  The row node of each pair is moved onto its column node; a row node is
+    brought below 1 first (an exact power of two), so that r <= 3 x (4 x 2^-24)^2 = 1.7e-13 stays well clear of the epsilon in fp32 and fp64."""
+    a = t["aggx"] * 100.0
+    flat = a.view(-1)
+    pick = torch.randperm(flat.numel(), generator=g)[:8]
+    flat[pick] = torch.tensor([100.0, -100.0] * 4, dtype=a.dtype)[:pick.numel()]
+    t["aggx"] = a
+    if not cfg.norm or ei.size(1) == 0:
+        return
+    src, x = t["QX_src"], t["x"]
+    moved, anchor, done = set(), set(), 0
+    for e in torch.randperm(ei.size(1), generator=g).tolist():
+        r, c = int(ei[0, e]), int(ei[1, e])               # table numbering
+        if r in moved or r in anchor or c in moved:
+            continue
+        xc = src[c, H:H + 3].clone()
+        big = float(xc.abs().max())
+        if big >= 1.0:                                    # (only an anchor nobody has used yet is rescaled)
+            if c in anchor:
+                continue
+            xc = xc * 2.0 ** -(int(torch.floor(torch.log2(torch.tensor(big)))) + 1)
+            src[c, H:H + 3] = xc
+            if row_begin <= c < row_begin + x.size(0):
+                x[c - row_begin] = xc
+        k = torch.randint(1, 5, (3,), generator=g).double() * (torch.randint(0, 2, (3,), generator=g).double() * 2 - 1)
+        xr = xc.clone() if done % 3 == 2 else _ulps(xc, k)     # every third pair coincides: a graph too small for twelve pairs has both kinds
+        x[r - row_begin] = xr
+        src[r, H:H + 3] = xr
+        moved.add(r); anchor.add(c)
+        done += 1
+        if done == 12:
+            break
+
+
 @functools.lru_cache(maxsize=None)
 def make_case(sizes: Tuple[int, ...], C: int, ea: int, na: int, flags: Tuple[str, ...], graph_kind: str = "random",
-              seed: int = 0) -> Case:
+              seed: int = 0, wiring: tuple = FASTEGNN_WIRING, act: tuple = SILU) -> Case:
     from fastegnn_amd._lib import PARAM_SLOTS
     sizes, flags = tuple(sizes), tuple(flags)
-    cfg = config(C, ea, na, flags)
+    cfg = config(C, ea, na, flags, wiring, act)
     N, B = sum(sizes), len(sizes)
     sub = graph_kind == "subrange"
     n_src, row_begin = (N + 37, 19) if sub else (N, 0)
@@ -154,8 +246,7 @@ def make_case(sizes: Tuple[int, ...], C: int, ea: int, na: int, flags: Tuple[str
     def rnd(*shape):
         return torch.randn(*shape, generator=g, dtype=torch.float32).double()
 
-    # O(1) heads (coord_gain 1.0, not the 1e-3 of a fresh model): no output hides behind a small weight
-    p = {k: v.float().double() for k, v in R.init_params(cfg, seed=seed, coord_gain=1.0, dtype=torch.float64).items()}
+    p = _layer_params(cfg, wiring, seed)
     params = [p.get("gcl_0." + s) for s in PARAM_SLOTS]
     grads0 = [rnd(*w.shape) if w is not None else None for w in params]
     batch = torch.repeat_interleave(torch.arange(B), torch.tensor(sizes))
@@ -184,8 +275,19 @@ def make_case(sizes: Tuple[int, ...], C: int, ea: int, na: int, flags: Tuple[str
                      g_ea0=(max(E, 1), max(ea, 1)), g_na0=(N, max(na, 1))).items():
         t[k] = rnd(*s)
     name = f"{'x'.join(map(str, sizes))}c{C}e{ea}a{na}-{graph_kind}"
+    if wiring[0] == "egnn":
+        _egnn_operand_edges(cfg, t, ei, n_src, row_begin, g)
+    if wiring != FASTEGNN_WIRING or act != SILU:
+        name += "-" + wiring_tag(wiring, act)
+        return Case(name, cfg, flags, sizes, N, B, C, n_src, row_begin, graph_kind, params, grads0, ei, batch, t,
+                    key=(sizes, C, ea, na, flags, graph_kind, seed, wiring, act), wiring=wiring, act=act)
     return Case(name, cfg, flags, sizes, N, B, C, n_src, row_begin, graph_kind, params, grads0, ei, batch, t,
                 key=(sizes, C, ea, na, flags, graph_kind, seed))
+
+
+def wiring_tag(wiring: tuple, act: tuple) -> str:
+    w = wiring[0] + ("".join(("+v" if wiring[1] else "-v", "+norm" if wiring[2] else "")) if wiring[0] == "egnn" else "")
+    return w + ("" if act == SILU else f"-{act[0]}" + (f"{act[1]:g}" if act[1] else ""))
 
 
 def case_name(stage: str, case: Case, variant: str = "", build: str = "cpu") -> str:
@@ -300,11 +402,26 @@ class HipRunner(BandedPool):
         from fastegnn_amd.model import _Spec
         c = case.cfg
         key = (c.virtual_channels, c.edge_attr_nf, c.node_attr_nf, case.flags, det)
+        if case.wiring != FASTEGNN_WIRING or case.act != SILU:
+            key += (case.wiring, case.act)
         sp = _SPECS.get(key)
+        if sp is None and case.wiring[0] == "egnn":
+            from tests.gpu_util import act_module
+            m = fastegnn_amd.EGNN(1, 1, c.edge_attr_nf, H, activation=act_module(c), device="cuda", with_v=c.with_v, norm=c.norm)
+            m.deterministic = det
+            m._build_spec()
+            sp = _SPECS[key] = m._spec
+            present = [s is not None for s in sp.layer_slots[0]]
+            assert present == [w is not None for w in case.params], "parameter slots of the module and of the oracle differ"
         if sp is None:
-            m = fastegnn_amd.FastEGNN(1, c.node_attr_nf, c.edge_attr_nf, H, c.virtual_channels, device="cuda", n_layers=1,
-                                      residual=c.residual, attention=c.attention, normalize=c.normalize, tanh=c.tanh,
-                                      gravity=c.gravity, mlp_dtype=torch.bfloat16 if c.bf16 else torch.float32)
+            kw = {}
+            if case.act != SILU:
+                from tests.gpu_util import act_module
+                kw["act_fn"] = act_module(c)
+            cls = fastegnn_amd.FastRF if case.wiring[0] == "rf" else fastegnn_amd.FastEGNN
+            m = cls(1, c.node_attr_nf, c.edge_attr_nf, H, c.virtual_channels, device="cuda", n_layers=1,
+                    residual=c.residual, attention=c.attention, normalize=c.normalize, tanh=c.tanh,
+                    gravity=c.gravity, mlp_dtype=torch.bfloat16 if c.bf16 else torch.float32, **kw)
             if c.coords_agg == "sum":
                 m._extra_flags = m._extra_flags | K.F_COORDS_SUM
             sp = _SPECS[key] = _Spec(m, deterministic=det)
@@ -316,14 +433,22 @@ class HipRunner(BandedPool):
         """1.0 or log2(e): the units in which this library keeps P and Q for this operand mode (module docstring)"""
         bf = case.cfg.bf16
         if bf not in self._scale:
-            probe = make_case((16,), 1, 0, 0, ("bf16",) if bf else (), "none", seed=99)
-            got = run_stage(self, "node_pre_forward", probe, _raw=True)
-            ref = run_stage(CpuRunner(torch.float64), "node_pre_forward", probe)
-            r = float((got["P"] * ref["P"]).sum() / (ref["P"] * ref["P"]).sum())
-            s = min((1.0, LOG2E), key=lambda v: abs(v - r))
-            assert abs(r - s) < (2e-2 if bf else 1e-4), f"{self.name}: P is {r} x the pre-activation share: neither plain nor in units of ln 2"
-            self._scale[bf] = s
+            self._scale[bf] = self._probe(bf, FASTEGNN_WIRING, SILU)
+        if case.wiring != FASTEGNN_WIRING or case.act != SILU:      # probed once more under each wiring and activation: one library, one answer
+            key = (bf, case.wiring, case.act)
+            if key not in self._scale:
+                self._scale[key] = self._probe(bf, case.wiring, case.act)
+                assert self._scale[key] == self._scale[bf], f"{self.name}: P in other units under {wiring_tag(case.wiring, case.act)}"
         return self._scale[bf]
+
+    def _probe(self, bf, wiring, act):
+        probe = make_case((16,), 0 if wiring[0] == "egnn" else 1, 0, 0, ("bf16",) if bf else (), "none", 99, wiring, act)
+        got = run_stage(self, "node_pre_forward", probe, _raw=True)
+        ref = run_stage(CpuRunner(torch.float64), "node_pre_forward", probe)
+        r = float((got["P"] * ref["P"]).sum() / (ref["P"] * ref["P"]).sum())
+        s = min((1.0, LOG2E), key=lambda v: abs(v - r))
+        assert abs(r - s) < (2e-2 if bf else 1e-4), f"{self.name}: P is {r} x the pre-activation share: neither plain nor in units of ln 2"
+        return s
 
 
 _SPECS: dict = {}
@@ -361,6 +486,9 @@ def run_stage(rn, name: str, case: Case, null: bool = False, want: bool = True, 
         scale = 1.0 if scale is None else scale
         P_in, src_in = _true_pq(case, scale)
     spec = rn.spec(case, det)
+    rf, egnn = case.wiring[0] == "rf", case.wiring[0] == "egnn"
+    assert not (egnn and name not in EGNN_STAGES), f"{name}: the EGNN wiring has no per-graph stages"
+    assert not (null and (rf or egnn)), "a null h_out / g_h_out is an error under the rf and egnn wirings (test it as one)"
     grav = cfg.gravity is not None
     ea, na = cfg.edge_attr_nf, cfg.node_attr_nf
     edge = name in EDGE_STAGES
@@ -406,6 +534,11 @@ def run_stage(rn, name: str, case: Case, null: bool = False, want: bool = True, 
 
     def virt_forward_products():
         """npre, poolV, poolX of the backend under test, from its own virt_forward on the case's operands"""
+        if egnn:                                   # C = 0: no virtual buffers, no pools (fastegnn_amd/egnn.py)
+            inp("h", "A", "x", "vel", "aggm", "aggx", "svel")
+            b["x_out"], b["h_out"], b["npre"] = rn.new(N, 3), rn.new(N, H), rn.new(N, H)
+            call("virt_forward")
+            return
         inp("h", "A", "Bc", "x", "vel", "Z", "aggm", "aggx", "svel", "sgrav")
         if na:
             inp("node_attr")
@@ -424,6 +557,9 @@ def run_stage(rn, name: str, case: Case, null: bool = False, want: bool = True, 
 
     if name == "node_pre_forward":
         inp("h", "x")
+        if rf:
+            inp("vel")                             # the velocity head's operand (its detached norm)
+        # svel is an output under every wiring: without the head (EGNN, with_v=False) the kernel stores zeros, and so does the statement
         out("P", N, H); out("QX", N, QX_LD); out("A", N, H); out("svel", N)
         if grav:
             out("sgrav", N)
@@ -441,7 +577,8 @@ def run_stage(rn, name: str, case: Case, null: bool = False, want: bool = True, 
         out("aggm", N, H); out("aggx", N, 3)
     elif name == "virt_forward":
         virt_forward_products()
-        for k in ("x_out", "poolX") + (() if null else ("h_out", "poolV")):
+        # (rf: poolV is zeroed, not summed -- nothing pools v without node_model_virtual; the statement holds zeros)
+        for k in ("x_out", "h_out") if egnn else ("x_out", "poolX") + (() if null else ("h_out", "poolV")):
             outs[k] = b[k]
     elif name == "graph_post_forward":
         xsum()
@@ -466,17 +603,23 @@ def run_stage(rn, name: str, case: Case, null: bool = False, want: bool = True, 
         virt_forward_products()
         for k in ("h_out", "x_out", "poolV", "poolX"):
             b.pop(k, None)
-        inp("g_x_out", "g_poolX")
-        if not null:
-            inp("g_h_out", "g_poolV")
-        for k, s in dict(g_h=(N, H), g_x=(N, 3), g_A=(N, H), g_aggm=(N, H), g_aggx=(N, 3), g_svel=(N,), g_Bc=(B, C, H),
-                         g_Zp=(B, 3, C)).items():
+        if egnn:
+            inp("g_x_out", "g_h_out")
+        else:
+            inp("g_x_out", "g_poolX")
+            if not null:
+                inp("g_h_out", "g_poolV")
+        # g_svel = <g_x_out, vel> is written under every wiring (with_v=False: node_pre_backward does not read it)
+        shapes = dict(g_h=(N, H), g_x=(N, 3), g_A=(N, H), g_aggm=(N, H), g_aggx=(N, 3), g_svel=(N,))
+        if not egnn:
+            shapes.update(g_Bc=(B, C, H), g_Zp=(B, 3, C))
+        for k, s in shapes.items():
             out(k, *s)
         if grav:
             out("g_sgrav", N)
         if na and want and not null:
             acc("g_node_attr", t["g_na0"])
-        if rn.hip:
+        if rn.hip and not egnn:
             b["wg_virt"] = rn.scratch(be.wg_virt_floats(N, C, spec.flags))
     elif name == "graph_pre_backward":
         xsum()
@@ -501,6 +644,9 @@ def run_stage(rn, name: str, case: Case, null: bool = False, want: bool = True, 
             b["wg_edge"] = rn.scratch(be.wg_edge_floats(case.edge_index.size(1)))
     elif name == "node_pre_backward":
         inp("h", "g_P", "g_QX", "g_A", "g_svel", "g_sgrav", "g_xrow", "g_x_out", "svel")
+        if rf:
+            inp("vel")
+        # g_vel += svel x g_x_out under every wiring (with_v=False: the caller's svel is the zero table; here it is a draw)
         gx = torch.zeros(B, 4, dtype=torch.float64)
         if rn.hip:                                 # the kernels' g_xbar is [B,3] packed (in a [B,4]-sized scratch array)
             gx.view(-1)[:B * 3] = t["g_xbar"].reshape(-1)
@@ -592,12 +738,19 @@ def reference(name: str, case_key: tuple, variant: tuple, scale: float):
 BF16_FACTOR, BF16_FLOOR = 3.0, 5e-3      # tests/test_gpu_bf16.py: distance to the fp64 mirror <= 3 x the fp32 mirror's own + 5e-3
 
 
+LEDGER = None            # a list: every comparison is noted in it as (case, buffer, err / tolerance) -- the accuracy record of a run
+
+
 def _check(case, key, got, ref32, truth, bad, bf16):
     if not bool(torch.isfinite(got).all()):
         bad.append(f"{key}: {int((~torch.isfinite(got)).sum())} of {got.numel()} elements not finite (never written?)")
         return
     if truth.numel() == 0:
         return
+    if LEDGER is not None:
+        from tests.helpers import grad_tolerance
+        e_got, e_ref = rel_err(got, truth), rel_err(ref32, truth)
+        LEDGER.append((case, key, e_got / (BF16_FACTOR * e_ref + BF16_FLOOR if bf16 else grad_tolerance(case, key, e_ref))))
     if bf16:
         e_got, e_ref = rel_err(got, truth), rel_err(ref32, truth)
         if e_got > BF16_FACTOR * e_ref + BF16_FLOOR:
@@ -713,3 +866,123 @@ def variant_id(key, variant) -> str:
     sizes, C, ea, na, flags, kind = key
     v = ",".join(k for k, on in variant if on) + ",".join("no" + k for k, on in variant if not on)
     return f"{'x'.join(map(str, sizes))}c{C}e{ea}a{na}-{kind}-{'+'.join(flags) or 'plain'}" + (f"-{v}" if v else "")
+
+
+# --------------------------------------------------------------------------
+# the sibling wirings and the activation kinds (tests/test_gpu_stage_wirings.py): tables of their own, the matrix above is as it was.
+# A key here is the full argument tuple of make_case: (sizes, C, ea, na, flags, graph kind, seed, wiring, act)
+# --------------------------------------------------------------------------
+RF = ("rf",)
+RF_MATRIX = [
+    (S_ONE, 1, 0, 0, ALL_FLAGS, "none"),
+    (S_RAGGED, 3, 2, 0, ALL_FLAGS, "random"),
+    (S_RAGGED, 3, 2, 0, ("bf16",), "random"),
+    (S_65, 5, 7, 0, (), "deg32_33"),
+    (S_EMPTY, 4, 2, 0, ("gravity",), "random"),
+    (S_MANY, 16, 2, 0, ALL_FLAGS, "random"),
+]
+# (N, ea, graph kind) of the EGNN wiring, one graph each: 16-row tiles around N = 16, one node, degree 32 / 33, a hub, one column
+EGNN_SHAPES = [(1, 2, "none"), (15, 2, "random"), (16, 2, "random"), (17, 0, "none"), (17, 7, "random"), (65, 0, "deg32_33"),
+               (65, 7, "random"), (681, 2, "hub"), (681, 2, "one_col"), (681, 2, "random")]
+EGNN_EDGE_ONLY = [(65, 7, "subrange"), (681, 2, "subrange")]
+EDGE_LEVEL, NODE_LEVEL = ("edge_forward", "edge_backward"), ("node_pre_forward", "virt_forward", "virt_backward", "node_pre_backward")
+
+# (Config.act, Config.act_param); the kinked kinds -- a derivative that jumps at 0 -- run at seeds chosen so that no pre-activation of the
+# fp64 reference lies within 1e-5 of 0 (KINK_SEEDS; tests/test_stage_harness_cpu.py asserts it), and stay at the small shapes for that
+KINDS = [("relu", 0.0), ("leaky_relu", 0.2), ("tanh", 0.0), ("sigmoid", 0.0), ("elu", 1.3), ("gelu", 0.0), ("softplus", 1.7)]
+KINKED = ("relu", "leaky_relu", "elu")
+KINK_BAND = 1e-5
+ACT_SHAPES = [(S_RAGGED, 3, 2, 1, ALL_FLAGS, "random"), (S_65, 5, 7, 0, ALL_FLAGS, "deg32_33"), (S_EMPTY, 4, 2, 0, (), "random")]
+ACT_SMOOTH_SHAPES = [(S_ONE, 1, 0, 0, ALL_FLAGS, "none"), (S_MANY, 16, 2, 0, ALL_FLAGS, "random"), (S_MANY, 33, 1, NA_MAX, ("attention",), "hub")]
+ACT_X3 = [(k, sh) for k in (("sigmoid", 0.0), ("gelu", 0.0)) for sh in (ACT_SHAPES[0], ACT_SMOOTH_SHAPES[1])]
+# act(0) != 0: once under each sibling wiring as well
+ACT_SIBLINGS = [(k, w, sh) for k in (("sigmoid", 0.0), ("softplus", 1.7))
+                for w, sh in ((RF, (S_RAGGED, 3, 2, 0, ALL_FLAGS, "random")), (("egnn", True, False), ((17,), 0, 7, 0, (), "random")),
+                              (("egnn", True, False), ((65,), 0, 0, 0, (), "deg32_33")))]
+# (kind, index into ACT_SHAPES, stage) -> the smallest seed >= 0 whose fp64 reference has no pre-activation with |z| < KINK_BAND
+KINK_SEEDS = {(kind, i, st): seed for (kind, i), seeds in {
+    # in the order of STAGES: node_pre_f, graph_xsum, graph_pre_f, edge_f, virt_f, graph_post_f, graph_post_b, virt_b, graph_pre_b, edge_b, node_pre_b
+    # (a stage that runs virt_forward for its operands counts that call's pre-activations too; the 65-node degree-32/33 shape evaluates
+    # 400 000 pre-activations in its edge stage: its first clean seed is in the thousands)
+    ("relu", 0): (0, 0, 0, 3, 1, 1, 1, 1, 0, 3, 0),
+    ("relu", 1): (2, 0, 0, 5057, 38, 38, 38, 38, 0, 5057, 2),
+    ("relu", 2): (0, 0, 0, 1, 1, 1, 1, 1, 0, 1, 0),
+    ("leaky_relu", 0): (0, 0, 0, 2, 3, 3, 3, 3, 0, 2, 0),
+    ("leaky_relu", 1): (2, 0, 0, 10398, 29, 29, 29, 29, 0, 10398, 2),
+    ("leaky_relu", 2): (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0),
+    ("elu", 0): (0, 0, 0, 0, 2, 2, 2, 2, 0, 0, 0),
+    ("elu", 1): (2, 0, 0, 3581, 0, 0, 0, 0, 0, 3581, 2),
+    ("elu", 2): (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0),
+}.items() for st, seed in zip(STAGES, seeds)}
+
+
+def min_abs_preactivation(stage: str, key: tuple) -> float:
+    """min |z| over every pre-activation the fp64 statement of `stage` evaluates on the case (inf: the stage has no activation)"""
+    from oracle.factored import track_min_abs_z
+    with track_min_abs_z() as tr:
+        run_stage(CpuRunner(torch.float64), stage, make_case(*key))
+    return tr.value
+
+
+def _variants(stage, k, wiring):
+    sizes, C, ea, na, flags, kind = k[:6]
+    out = [()]
+    if stage == "edge_backward":
+        out.append((("det", True),))
+        if ea > 0 and (sizes, kind) in ((S_RAGGED, "random"), (S_65, "deg32_33")):
+            out.append((("want", False),))
+    if stage == "virt_backward" and na > 0:
+        out.append((("want", False),))
+    return out
+
+
+def rf_cases(stage: str, duplicate: bool = False):
+    """duplicate: the run on a second build of the same kernels, without the variants"""
+    return [(k + (0, RF, SILU), v) for k in RF_MATRIX for v in (_variants(stage, k, RF)[:1] if duplicate else _variants(stage, k, RF))]
+
+
+def egnn_cases(stage: str, duplicate: bool = False):
+    """the six stages of the EGNN wiring; with_v and norm on and off where the stage can see them: norm lives in the edge stage,
+    the velocity head in the node-level stages (the other switch is crossed in at N = 17).  duplicate: the run on a second build of
+    the same kernels -- the first setting of a shape, and norm in the edge stages; without N = 15, 16 and the one-column graph"""
+    out = []
+    shapes = EGNN_SHAPES + (EGNN_EDGE_ONLY if stage in EDGE_LEVEL else [])
+    if duplicate:
+        shapes = [sh for sh in shapes if sh[0] not in (15, 16) and sh[2] != "one_col"]
+    for n, ea, kind in shapes:
+        if stage in EDGE_LEVEL:
+            combos = [(True, False), (True, True)] + ([(False, True)] if n == 17 else [])
+        else:
+            combos = [(True, False), (False, False)] + ([(False, True)] if n == 17 else [])
+        for with_v, norm in (combos[:2 if stage in EDGE_LEVEL else 1] if duplicate else combos):
+            k = ((n,), 0, ea, 0, (), kind, 0, ("egnn", with_v, norm), SILU)
+            out += [(k, v) for v in [()] + ([(("det", True),)] if stage == "edge_backward" else [])]
+    return out
+
+
+def act_cases(stage: str):
+    """FastEGNN wiring on the generic-activation build: every kind at ACT_SHAPES (the kinked ones at their committed seeds), the
+    smooth kinds at the larger shapes too, and the null wiring of NULL_STAGES at the ragged shape"""
+    out = []
+    for kind in KINDS:
+        for i, sh in enumerate(ACT_SHAPES):
+            seed = KINK_SEEDS[(kind[0], i, stage)] if kind[0] in KINKED else 0
+            k = sh + (seed, FASTEGNN_WIRING, kind)
+            out += [(k, v) for v in _variants(stage, k, FASTEGNN_WIRING)]
+            if stage in NULL_STAGES and sh[0] == S_RAGGED and kind[0] not in KINKED:
+                out.append((k, (("null", True),)))
+        if kind[0] not in KINKED:
+            out += [(sh + (0, FASTEGNN_WIRING, kind), ()) for sh in ACT_SMOOTH_SHAPES]
+    return out
+
+
+def act_x3_cases(stage: str):
+    return [(sh + (0, FASTEGNN_WIRING, kind), ()) for kind, sh in ACT_X3]
+
+
+def act_sibling_cases(stage: str):
+    return [(sh + (0, w, kind), ()) for kind, w, sh in ACT_SIBLINGS if w[0] != "egnn" or stage in EGNN_STAGES]
+
+
+def wiring_case_id(key, variant) -> str:
+    return variant_id(key[:6], variant) + "-" + wiring_tag(key[7], key[8]) + (f"-s{key[6]}" if key[6] else "")

@@ -156,3 +156,44 @@ def test_fastrf_other_activation_vs_oracle(act, q, h):
         got = prm.grad.cpu() if prm.grad is not None else torch.zeros_like(prm).cpu()
         grad_check(f"act_mid_fastrf_{act}_attention", k, got, g32[k], g64[k], bad)
     assert not bad, bad
+
+
+def test_fastrf_deterministic_vs_oracle_and_repeatable_coordinate_gradient():
+    """deterministic=True on the FastRF wiring (FASTEGNN_F_DETERMINISTIC | FASTEGNN_F_RF): every gradient against the oracle at ~300 nodes, and the
+    coordinate gradient -- which ends in the col-keyed sum the flag orders -- bit-identical over two backward passes"""
+    from oracle import fastegnn_ref as R
+    from tests.test_gpu_properties import _batch
+    C = 3
+    cfg = R.Config(2, 0, 2, 64, C, n_layers=2, gravity=[0, -1, 0])
+    inp = _batch([170, 1, 130], 6, C, seed=37)
+    torch.manual_seed(12)
+    m = fastegnn_amd.FastRF(2, 0, 2, 64, C, device="cuda", n_layers=2, gravity=[0, -1, 0])
+    m.deterministic = True
+    tgt = inp["node_loc"] + 0.5
+    gx = []
+    for _ in range(2):
+        m.zero_grad(set_to_none=True)
+        kw = {k: v.cuda() for k, v in inp.items()}
+        kw["node_loc"].requires_grad_(True)
+        loc, vloc = m(**kw)
+        (torch.nn.functional.mse_loss(loc, tgt.cuda()) + 0.05 * vloc.pow(2).mean()).backward()
+        gx.append(kw["node_loc"].grad.clone())
+    assert m._spec.flags & fastegnn_amd._lib.F_DETERMINISTIC and m._spec.flags & fastegnn_amd._lib.F_RF
+    assert torch.equal(gx[0].view(torch.int32), gx[1].view(torch.int32))
+    res = {}
+    for dt in (torch.float32, torch.float64):
+        p = {k: v.detach().cpu().to(dt).requires_grad_(True) for k, v in m.state_dict().items()}
+        ii = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in inp.items()}
+        ii["node_loc"] = ii["node_loc"].clone().requires_grad_(True)
+        l, v = RF.forward(p, cfg, **ii)
+        (torch.nn.functional.mse_loss(l, tgt.to(dt)) + 0.05 * v.pow(2).mean()).backward()
+        res[dt] = (l.detach(), v.detach(), {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in p.items()}, ii["node_loc"].grad)
+    l32, v32, g32, x32 = res[torch.float32]
+    _, _, g64, x64 = res[torch.float64]
+    assert rel_err(loc, l32) < OUT_TOL and rel_err(vloc, v32) < OUT_TOL
+    bad = []
+    for k, prm in m.named_parameters():
+        got = prm.grad.cpu() if prm.grad is not None else torch.zeros_like(prm).cpu()
+        grad_check("test_fastrf_deterministic", k, got, g32[k], g64[k], bad)
+    grad_check("test_fastrf_deterministic", "gin/node_loc", gx[1].cpu(), x32, x64, bad)
+    assert not bad, bad

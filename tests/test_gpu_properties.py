@@ -636,3 +636,11 @@ def test_stage_level_api_world1_matches_whole_layer_path():
     assert rel_err(outs[1][0], outs[0][0]) < 1e-6 and rel_err(outs[1][1], outs[0][1]) < 1e-6
     assert rel_err(outs[1][2], outs[0][2]) < 1e-5
     dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("act,q", [("sigmoid", 0.0), ("softplus", 1.7)])
+def test_activations_that_do_not_vanish_at_zero_small_ragged_vs_oracle(act, q):
+    """Sigmoid and Softplus on the fused path: act(0) = 0.5 / ln 2 / beta, so a padding row or padding edge of a ragged tile whose zero
+    pre-activation reached a sum would show -- graphs of 33, 1 and 17 nodes, C = 3, two layers, gates on"""
+    cfg = R.Config(2, 0, 2, 64, 3, n_layers=2, attention=True, act=act, act_param=q)
+    _check_vs_oracle(cfg, _batch([33, 1, 17], 5, 3, seed=71), seed=71, case=f"test_small_ragged_{act}")
