@@ -213,6 +213,9 @@ def lib(act: bool = False, wide=None):
     L.fastegnn_rollout_plan.argtypes = [_vp, _i32, _vp, C.c_int64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]
     L.fastegnn_rollout_advance.argtypes = [_vp, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.fastegnn_rollout_graph.argtypes = [_vp, _i32, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _i32, _vp, _vp, _vp]
+    # the same two in a rotated and shifted frame (include/fastegnn_hip.h "rigid motions"): additive
+    L.fastegnn_traj_gather_moved.argtypes = [_vp, _vp, _i32, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64] + [_vp] * 6 + [_vp, _i32, _vp]
+    L.fastegnn_rollout_graph_moved.argtypes = [_vp, _i32, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _i32, _vp, _vp, _vp, _i32, _vp]
     # a training step's (loss, mse) into the epoch's three fp64 words: additive
     L.fastegnn_loss_accumulate.argtypes = [_vp, _vp, _i32, _vp, _vp]
     # the training loss without floating-point atomics (its workspace query and the entry point that takes one): additive
@@ -317,6 +320,7 @@ EXPORTED = STAGE_FUNCS + [
     "fastegnn_cutoff_batch_tmp_bytes", "fastegnn_cutoff_edges_batch", "fastegnn_collate_plan", "fastegnn_collate_gather",
     "fastegnn_collate_graph", "fastegnn_collate_draw", "fastegnn_collate_gather_uniform", "fastegnn_traj_plan", "fastegnn_traj_gather",
     "fastegnn_traj_mean", "fastegnn_rollout_plan", "fastegnn_rollout_advance", "fastegnn_rollout_graph", "fastegnn_loss_accumulate",
+    "fastegnn_traj_gather_moved", "fastegnn_rollout_graph_moved",
     "fastegnn_loss_ordered_ws_doubles", "fastegnn_loss_mse_mmd_ordered",
     "fastegnn_profile_enable", "fastegnn_profile_kernels", "fastegnn_profile_name", "fastegnn_profile_collect",
     "fastegnn_comm_unique_id_bytes", "fastegnn_comm_unique_id", "fastegnn_comm_init", "fastegnn_comm_destroy", "fastegnn_comm_rank",

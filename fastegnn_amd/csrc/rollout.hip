@@ -6,6 +6,8 @@
 //            error against the truth frame, sse[b], in fp64 in the same order
 // and once per rollout
 //   plan     truth_rows [steps,B]: the first row in pos of the truth frame of step k for slot b, -1 beyond the trajectory's end
+// A rollout over a dataset with a rigid motion per sample scores with `graph_moved`: the same launch, the truth rows moved by the slot's
+// motion in fp32 (the rule of traj.hip's moved gather) before the fp64 difference.
 // No atomics, no workspace, nothing read back, 64-bit offsets.  Sample ids, trajectory and frame numbers are clamped as traj.hip's plan
 // clamps them; a graph whose node range does not lie inside [0, N) or whose truth rows do not lie inside pos is skipped: nothing is read
 // outside the tables and nothing is written beyond the sizes the host gave, whatever the device arrays hold.
@@ -99,11 +101,28 @@ __device__ __forceinline__ double ro_sq3(double dx, double dy, double dz) {
   return (xx + yy) + zz;
 }
 
+// The rigid motion of include/fastegnn_hip.h ("rigid motions"), traj.hip's tj_move: q[j] = ((p[0]*R[0][j] + p[1]*R[1][j]) + p[2]*R[2][j]),
+// every operation rounded to fp32 by itself, then + t[j] when `shift` (no addition at all without it).  m: R row-major, then t.
+__device__ __forceinline__ void ro_move(const float (&m)[12], const float (&p)[3], bool shift, float (&q)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float a = p[0] * m[j];
+    const float b = p[1] * m[3 + j];
+    const float c = p[2] * m[6 + j];
+    const float r = (a + b) + c;
+    q[j] = shift ? r + m[9 + j] : r;
+  }
+}
+
+// MOVED: the truth row is moved by graph b's motion (motion row b, b = the workgroup: below B) in fp32 before the fp64 difference
+template <bool MOVED>
 __global__ __launch_bounds__(RO_GRAPH_THREADS) void rollout_graph_kernel(const int64_t *__restrict__ ptr, const float *__restrict__ loc,
                                                                           const float *__restrict__ x_new, long long N,
                                                                           const float *__restrict__ pos, long long pos_rows,
                                                                           const int64_t *__restrict__ truth_rows, int C,
-                                                                          float *__restrict__ loc_mean, double *__restrict__ sse) {
+                                                                          float *__restrict__ loc_mean, double *__restrict__ sse,
+                                                                          const float *__restrict__ motion, int has_t) {
   __shared__ double part[4][RO_GRAPH_THREADS];
   const int b = blockIdx.x, t = threadIdx.x;
   const long long at = ptr[b];
@@ -112,14 +131,28 @@ __global__ __launch_bounds__(RO_GRAPH_THREADS) void rollout_graph_kernel(const i
   const bool score = sse != nullptr;
   long long r = score ? truth_rows[b] : -1;
   if (r < 0 || r > pos_rows - n) r = -1;      // no truth frame, or its rows are not inside pos: no score
+  float m[12] = {};
+  if (MOVED && r >= 0) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = motion[(long long)b * 12 + k];
+  }
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   for (long long i = t; i < n; i += RO_GRAPH_THREADS) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] += (double)loc[(at + i) * 3 + k];
     if (r >= 0) {
+      float p[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) p[k] = pos[(r + i) * 3 + k];
+      if (MOVED) {
+        float q[3];
+        ro_move(m, p, has_t != 0, q);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = q[k];
+      }
       double d[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) d[k] = (double)x_new[(at + i) * 3 + k] - (double)pos[(r + i) * 3 + k];
+      for (int k = 0; k < 3; ++k) d[k] = (double)x_new[(at + i) * 3 + k] - (double)p[k];
       s[3] += ro_sq3(d[0], d[1], d[2]);
     }
   }
@@ -188,9 +221,25 @@ int fastegnn_rollout_graph(const int64_t *ptr, int32_t B, const float *loc, cons
   FE_REQUIRE(!sse || (x_new && pos && truth_rows), "rollout_graph: a score needs x_new, pos and truth_rows");
   hipStream_t st = (hipStream_t)stream;
   ProfScope _ps(K_MISC, st);
-  hipLaunchKernelGGL(rollout_graph_kernel, dim3(B), dim3(RO_GRAPH_THREADS), 0, st, ptr, loc, x_new, (long long)n_nodes, pos,
-                     (long long)pos_rows, truth_rows, C, loc_mean, sse);
+  hipLaunchKernelGGL(rollout_graph_kernel<false>, dim3(B), dim3(RO_GRAPH_THREADS), 0, st, ptr, loc, x_new, (long long)n_nodes, pos,
+                     (long long)pos_rows, truth_rows, C, loc_mean, sse, (const float *)nullptr, 0);
   return check_launch("rollout_graph");
+}
+
+int fastegnn_rollout_graph_moved(const int64_t *ptr, int32_t B, const float *loc, const float *x_new, int64_t n_nodes, const float *pos,
+                                 int64_t pos_rows, const int64_t *truth_rows, int32_t C, float *loc_mean, double *sse,
+                                 const float *motion, int32_t has_t, void *stream) {
+  FE_REQUIRE(C >= 1 && C <= (1 << 20), "rollout_graph_moved: C out of range (1 .. 2^20)");
+  FE_REQUIRE(B >= 0 && n_nodes >= 0 && pos_rows >= 0, "rollout_graph_moved: negative size");
+  if (B == 0) return FASTEGNN_OK;
+  FE_REQUIRE(ptr && loc_mean && (loc || n_nodes == 0), "rollout_graph_moved: null pointer");
+  FE_REQUIRE(!sse || (x_new && pos && truth_rows), "rollout_graph_moved: a score needs x_new, pos and truth_rows");
+  FE_REQUIRE(!sse || motion, "rollout_graph_moved: a score needs the motion table");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope _ps(K_MISC, st);
+  hipLaunchKernelGGL(rollout_graph_kernel<true>, dim3(B), dim3(RO_GRAPH_THREADS), 0, st, ptr, loc, x_new, (long long)n_nodes, pos,
+                     (long long)pos_rows, truth_rows, C, loc_mean, sse, motion, has_t);
+  return check_launch("rollout_graph_moved");
 }
 
 }  // extern "C"

@@ -7,6 +7,9 @@
 //   gather  one launch over the N nodes: loc_0, loc_t, vel_0, node_feat, node_attr, batch.  A tile finds the slots it touches by a
 //           binary search in ptr; a tile inside one slot searches nothing per node (collate.hip's gather)
 //   mean    one workgroup per graph: loc_mean [B,3,C], summed in fp64 in one fixed order
+// A dataset with a rigid motion per sample (rotation / translation of TrajectoryDataset) runs `gather_moved` instead: the same launch
+// with the slot's motion applied to loc_0, loc_t and vel_0 before they are stored; its mean is taken over the moved loc_0
+// (rollout.hip's graph kernel), so that the node side is plan, the selection of the motion rows, gather_moved, mean: four launches.
 // No atomics, no workspace besides the outputs and the slot table, 64-bit offsets throughout.  Sample ids, trajectory numbers and frame
 // numbers are clamped, and a node whose source rows do not lie inside the tables is skipped: nothing is read outside pos / kind and
 // nothing is written beyond the sizes the host gave, whatever the device arrays hold.
@@ -35,6 +38,8 @@ struct TjBatch {
   const float *pos, *kind, *kind_scaled;
   long long pos_rows, kind_rows, N;
   int B;
+  const float *motion;   // [B, 12]: R row-major, then t (the moved gather alone)
+  int has_t;
 };
 
 struct TjOut {
@@ -129,9 +134,25 @@ __device__ __forceinline__ float tj_speed(float vx, float vy, float vz) {
   return sqrtf(s);
 }
 
+// The rigid motion of include/fastegnn_hip.h ("rigid motions"): q[j] = ((p[0]*R[0][j] + p[1]*R[1][j]) + p[2]*R[2][j]), every operation
+// rounded to fp32 by itself (contraction off, for tj_speed's reason: torch's elementwise restatement fuses nothing), then + t[j] when
+// `shift` -- without it no addition runs at all (p + 0.0f would turn -0.0 into +0.0).  m: the 12 values R row-major, then t.
+__device__ __forceinline__ void tj_move(const float (&m)[12], const float (&p)[3], bool shift, float (&q)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float a = p[0] * m[j];
+    const float b = p[1] * m[3 + j];
+    const float c = p[2] * m[6 + j];
+    const float r = (a + b) + c;
+    q[j] = shift ? r + m[9 + j] : r;
+  }
+}
+
 // One tile of TJ_TILE nodes.  UNIFORM: the whole tile lies in slot flo (its segment is the same for every lane and is loaded once);
-// otherwise every node finds its slot in [flo, fhi].
-template <bool UNIFORM>
+// otherwise every node finds its slot in [flo, fhi].  MOVED: the slot's motion (P.motion, row = the slot, which is below B) is applied
+// to the three vectors before they are stored and before the speed is taken; a UNIFORM tile loads its 12 values once.
+template <bool UNIFORM, bool MOVED = false>
 __device__ __forceinline__ void traj_tile(const TjBatch &P, const TjOut &O, long long e0, long long e1, int flo, int fhi) {
   // a node that is skipped keeps row 0 of both tables as its source: every load below is unconditional (a load under a per-node
   // condition is branched around and waited for by itself), and the host call requires both tables to hold a row
@@ -174,14 +195,41 @@ __device__ __forceinline__ void traj_tile(const TjBatch &P, const TjOut &O, long
     kd[u] = P.kind[pk[u]];
     ks[u] = P.kind_scaled[pk[u]];
   }
+  // the motions: one row for a UNIFORM tile, else the row of every node's slot -- slot[u] lies in [flo, fhi], below B, also for a node
+  // that is skipped (it keeps flo), so these loads are unconditional as well
+  constexpr int TJ_ROWS = MOVED ? (UNIFORM ? 1 : TJ_UNROLL) : 1;
+  float mo[TJ_ROWS][12] = {};
+  if (MOVED) {
+#pragma unroll
+    for (int u = 0; u < TJ_ROWS; ++u) {
+      const long long row = UNIFORM ? flo : slot[u];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) mo[u][k] = P.motion[row * 12 + k];
+    }
+  }
 #pragma unroll
   for (int u = 0; u < TJ_UNROLL; ++u) {
     if (!on[u]) continue;
     const long long e = e0 + u * TJ_THREADS + threadIdx.x;
     float v[3];
 #pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = b[u][k] - a[u][k];   // the difference first, then its rotation
+    if (MOVED) {
+      const float (&m)[12] = mo[UNIFORM ? 0 : u];
+      const bool shift = P.has_t != 0;
+      float qa[3], qc[3], qv[3];
+      tj_move(m, a[u], shift, qa);
+      tj_move(m, c[u], shift, qc);
+      tj_move(m, v, false, qv);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        a[u][k] = qa[k];
+        c[u][k] = qc[k];
+        v[k] = qv[k];
+      }
+    }
+#pragma unroll
     for (int k = 0; k < 3; ++k) {
-      v[k] = b[u][k] - a[u][k];
       O.loc_0[e * 3 + k] = a[u][k];
       O.loc_t[e * 3 + k] = c[u][k];
       O.vel_0[e * 3 + k] = v[k];
@@ -201,6 +249,17 @@ __global__ __launch_bounds__(TJ_THREADS) void traj_gather_kernel(const TjBatch P
     const int fhi = tj_find_slot(P.ptr, flo, P.B - 1, e1 - 1);
     if (flo == fhi) traj_tile<true>(P, O, e0, e1, flo, fhi);
     else traj_tile<false>(P, O, e0, e1, flo, fhi);
+  }
+}
+
+__global__ __launch_bounds__(TJ_THREADS) void traj_gather_moved_kernel(const TjBatch P, const TjOut O, const long long n_tiles) {
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long long e0 = tile * TJ_TILE;
+    const long long e1 = e0 + TJ_TILE < P.N ? e0 + TJ_TILE : P.N;
+    const int flo = tj_find_slot(P.ptr, 0, P.B - 1, e0);
+    const int fhi = tj_find_slot(P.ptr, flo, P.B - 1, e1 - 1);
+    if (flo == fhi) traj_tile<true, true>(P, O, e0, e1, flo, fhi);
+    else traj_tile<false, true>(P, O, e0, e1, flo, fhi);
   }
 }
 
@@ -281,21 +340,34 @@ int fastegnn_traj_plan(const int64_t *ids, int32_t B, const int64_t *samples, in
   return check_launch("traj_plan");
 }
 
-int fastegnn_traj_gather(const int64_t *ptr, const int64_t *slots, int32_t B, int64_t n_nodes_out, const float *pos, int64_t pos_rows,
-                         const float *kind, const float *kind_scaled, int64_t kind_rows, float *loc_0, float *loc_t, float *vel_0,
-                         float *node_feat, float *node_attr, int64_t *batch_out, void *stream) {
-  FE_REQUIRE(n_nodes_out >= 0 && kind_rows >= 0, "traj_gather: negative size");
+// _gather and _gather_moved: the same checks, the same grid; `moved` picks the kernel
+static int tj_gather(const char *who, const int64_t *ptr, const int64_t *slots, int32_t B, int64_t n_nodes_out, const float *pos,
+                     int64_t pos_rows, const float *kind, const float *kind_scaled, int64_t kind_rows, float *loc_0, float *loc_t,
+                     float *vel_0, float *node_feat, float *node_attr, int64_t *batch_out, bool moved, const float *motion, int32_t has_t,
+                     void *stream) {
+  const std::string w(who);
+  if (n_nodes_out < 0 || kind_rows < 0) {
+    set_error(w + ": negative size");
+    return FASTEGNN_E_INVALID;
+  }
   TjBatch P;
-  const int rc = tj_batch(P, "traj_gather", ptr, slots, B, pos, pos_rows, n_nodes_out > 0);
+  const int rc = tj_batch(P, who, ptr, slots, B, pos, pos_rows, n_nodes_out > 0);
   if (rc != FASTEGNN_OK) return rc;
   if (B == 0 || n_nodes_out == 0) return FASTEGNN_OK;   // nothing to write: no launch on an empty grid
-  FE_REQUIRE(kind && kind_scaled, "traj_gather: null pointer");
-  FE_REQUIRE(pos_rows >= 1 && kind_rows >= 1, "traj_gather: nodes asked for from empty tables");
-  FE_REQUIRE(loc_0 && loc_t && vel_0 && node_feat && node_attr && batch_out, "traj_gather: null output");
+  const char *bad = nullptr;
+  if (!kind || !kind_scaled || (moved && !motion)) bad = ": null pointer";
+  else if (pos_rows < 1 || kind_rows < 1) bad = ": nodes asked for from empty tables";
+  else if (!loc_0 || !loc_t || !vel_0 || !node_feat || !node_attr || !batch_out) bad = ": null output";
+  if (bad) {
+    set_error(w + bad);
+    return FASTEGNN_E_INVALID;
+  }
   P.kind = kind;
   P.kind_scaled = kind_scaled;
   P.kind_rows = kind_rows;
   P.N = n_nodes_out;
+  P.motion = motion;
+  P.has_t = has_t;
   TjOut O;
   O.loc_0 = loc_0;
   O.loc_t = loc_t;
@@ -307,8 +379,24 @@ int fastegnn_traj_gather(const int64_t *ptr, const int64_t *slots, int32_t B, in
   const int grid = (int)(n_tiles < TJ_MAX_BLOCKS ? n_tiles : TJ_MAX_BLOCKS);
   hipStream_t st = (hipStream_t)stream;
   ProfScope _ps(K_MISC, st);
-  hipLaunchKernelGGL(traj_gather_kernel, dim3(grid), dim3(TJ_THREADS), 0, st, P, O, n_tiles);
-  return check_launch("traj_gather");
+  if (moved) hipLaunchKernelGGL(traj_gather_moved_kernel, dim3(grid), dim3(TJ_THREADS), 0, st, P, O, n_tiles);
+  else hipLaunchKernelGGL(traj_gather_kernel, dim3(grid), dim3(TJ_THREADS), 0, st, P, O, n_tiles);
+  return check_launch(who);
+}
+
+int fastegnn_traj_gather(const int64_t *ptr, const int64_t *slots, int32_t B, int64_t n_nodes_out, const float *pos, int64_t pos_rows,
+                         const float *kind, const float *kind_scaled, int64_t kind_rows, float *loc_0, float *loc_t, float *vel_0,
+                         float *node_feat, float *node_attr, int64_t *batch_out, void *stream) {
+  return tj_gather("traj_gather", ptr, slots, B, n_nodes_out, pos, pos_rows, kind, kind_scaled, kind_rows, loc_0, loc_t, vel_0, node_feat,
+                   node_attr, batch_out, false, nullptr, 0, stream);
+}
+
+int fastegnn_traj_gather_moved(const int64_t *ptr, const int64_t *slots, int32_t B, int64_t n_nodes_out, const float *pos,
+                               int64_t pos_rows, const float *kind, const float *kind_scaled, int64_t kind_rows, float *loc_0,
+                               float *loc_t, float *vel_0, float *node_feat, float *node_attr, int64_t *batch_out, const float *motion,
+                               int32_t has_t, void *stream) {
+  return tj_gather("traj_gather_moved", ptr, slots, B, n_nodes_out, pos, pos_rows, kind, kind_scaled, kind_rows, loc_0, loc_t, vel_0,
+                   node_feat, node_attr, batch_out, true, motion, has_t, stream);
 }
 
 int fastegnn_traj_mean(const int64_t *ptr, const int64_t *slots, int32_t B, const float *pos, int64_t pos_rows, int32_t C,

@@ -837,7 +837,8 @@ def _upload_ids(ids: torch.Tensor, device) -> torch.Tensor:
 
 class HipTrajOps:
     """The device calls of a trajectory batch on libfastegnn_hip.so (the product path): ``plan``, ``gather`` and ``mean`` are the three
-    launches of its node side (include/fastegnn_hip.h, fastegnn_traj_*), ``edges`` the two batched graph calls ``water3d_batch`` makes.
+    launches of its node side (include/fastegnn_hip.h, fastegnn_traj_*), ``edges`` the two batched graph calls ``water3d_batch`` makes;
+    ``gather_moved`` and ``mean_of`` replace ``gather`` and ``mean`` for a batch with a rigid motion per slot (tests/motion_ref.py).
     tests/trajectory_ref.py restates the first three in torch, so that tests/test_trajectory_cpu.py can drive the orchestration
     without a GPU (the ``HipCollateOps`` precedent)."""
 
@@ -876,6 +877,34 @@ class HipTrajOps:
                                            K.ptr(loc_mean), _stream(ptr.device)), "fastegnn_traj_mean")
 
     @staticmethod
+    def gather_moved(ptr, slots, n_nodes, pos, kind, kind_scaled, loc_0, loc_t, vel_0, node_feat, node_attr, batch_out, motion,
+                     has_t) -> None:
+        """``gather`` with the rigid motion ``motion[b]`` (fp32 [B,12]: R row-major, then t) applied to slot b in the same launch, by
+        the rule of ``apply_motion``; ``has_t`` false: no translation is added (the t values are not used)"""
+        if not ptr.is_cuda:
+            raise RuntimeError(_NO_CPU_TRAJ)
+        B = ptr.numel() - 1
+        if not (motion.is_cuda and motion.dtype == torch.float32 and tuple(motion.shape) == (B, 12) and motion.is_contiguous()):
+            raise ValueError(f"fastegnn_amd: the motion rows of a batch of {B} samples must be a contiguous device fp32 [{B},12] tensor")
+        from . import _lib as K
+        from .model import _stream
+        K.check(K.lib().fastegnn_traj_gather_moved(K.ptr(ptr), K.ptr(slots), B, int(n_nodes), K.ptr(pos), pos.size(0), K.ptr(kind),
+                                                   K.ptr(kind_scaled), kind.size(0), K.ptr(loc_0), K.ptr(loc_t), K.ptr(vel_0),
+                                                   K.ptr(node_feat), K.ptr(node_attr), K.ptr(batch_out), K.ptr(motion), int(bool(has_t)),
+                                                   _stream(ptr.device)), "fastegnn_traj_gather_moved")
+
+    @staticmethod
+    def mean_of(ptr, loc, loc_mean) -> None:
+        """loc_mean [B,3,C] <- per slot the fp64 mean of the rows ``ptr[b] .. ptr[b+1]`` of ``loc`` [N,3], by ``mean``'s rule (the
+        graph launch of csrc/rollout.hip without a score)"""
+        if not ptr.is_cuda:
+            raise RuntimeError(_NO_CPU_TRAJ)
+        from . import _lib as K
+        from .model import _stream
+        K.check(K.lib().fastegnn_rollout_graph(K.ptr(ptr), ptr.numel() - 1, K.ptr(loc), None, loc.size(0), None, 0, None,
+                                               loc_mean.size(2), K.ptr(loc_mean), None, _stream(ptr.device)), "fastegnn_rollout_graph")
+
+    @staticmethod
     def edges(loc_0, ptr, ptr_host, radius, cutoff_rate):
         """(edge_index with global ids, dist) of the clouds ``loc_0[ptr[b]:ptr[b+1]]``: the two calls of ``_water3d_batch_edges``, in
         its order.  ``ptr`` is the device tensor the plan wrote and ``ptr_host`` the same offsets from the host's node counts: the
@@ -891,6 +920,80 @@ _TRAJ_OPS = HipTrajOps
 
 def _as_host_tensor(a) -> torch.Tensor:
     return a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+
+
+def apply_motion(x: torch.Tensor, R, t=None) -> torch.Tensor:
+    """The rigid-motion rule of include/fastegnn_hip.h ("rigid motions") in torch: for the rows of ``x`` [n,3]
+
+        q[:, j] = (x[:, 0] * R[0, j] + x[:, 1] * R[1, j]) + x[:, 2] * R[2, j]           then  q + t  when ``t`` is given
+
+    -- the reference's ``x @ R (+ t)`` in one fixed evaluation order.  Every product and sum is one eager elementwise fp32 operation,
+    rounded by itself, so the result has the bits of ``fastegnn_traj_gather_moved`` / ``fastegnn_rollout_graph_moved`` on either
+    device (``x @ R`` has not: a matrix product may fuse and reorder).  A position is moved with ``t``, a velocity without.  ``R``
+    [3,3] and ``t`` [3]: arrays or tensors, taken to ``x``'s device as fp32."""
+    R = torch.as_tensor(R).to(x.device, torch.float32)
+    q = (x[:, 0:1] * R[0] + x[:, 1:2] * R[1]) + x[:, 2:3] * R[2]
+    if t is not None:
+        q = q + torch.as_tensor(t).to(x.device, torch.float32)
+    return q
+
+
+def _host_array(a, who: str) -> np.ndarray:
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.dtype.kind not in "fiu" or not np.isfinite(a).all():
+        raise ValueError(f"TrajectoryDataset: {who} must be finite numbers")
+    return a.astype(np.float64)
+
+
+def _axis_rotations(deg: np.ndarray, axis: int) -> np.ndarray:
+    """fp64 [S,3,3]: the rotation by ``deg`` degrees about coordinate axis ``axis`` in the reference's sign convention
+    (``utils/rotate.py``: about x and z the ``-sin`` stands above the diagonal, about y below it)"""
+    th = np.radians(deg.astype(np.float64))
+    c, s = np.cos(th), np.sin(th)
+    a, b = [(1, 2), (2, 0), (0, 1)][axis]
+    M = np.zeros((deg.size, 3, 3))
+    M[:, axis, axis] = 1.0
+    M[:, a, a], M[:, b, b], M[:, a, b], M[:, b, a] = c, c, -s, s
+    return M
+
+
+def _motion_table(S: int, rotation, translation, motion_seed):
+    """(fp32 host array [S,12] = R row-major then t, has_t) of ``TrajectoryDataset(rotation=, translation=, motion_seed=)``, or
+    (None, False) without either.  One generator, ``default_rng(motion_seed)``: first the angles of every sample (integer degrees
+    from ``integers(0, 361)``: the reference's ``randint(0, 360)`` includes both ends), then the translations' ``standard_normal``."""
+    if rotation is None and translation is None:
+        return None, False
+    rng = np.random.default_rng(motion_seed)
+    if rotation is None:
+        R = np.broadcast_to(np.eye(3), (S, 3, 3))
+    elif isinstance(rotation, str):
+        if rotation == "y":
+            R = _axis_rotations(rng.integers(0, 361, size=S), 1)
+        elif rotation == "xyz":
+            deg = rng.integers(0, 361, size=(S, 3))
+            R = _axis_rotations(deg[:, 0], 0) @ _axis_rotations(deg[:, 1], 1) @ _axis_rotations(deg[:, 2], 2)
+        else:
+            raise ValueError(f"TrajectoryDataset: rotation must be None, 'y', 'xyz' or a [3,3] / [S,3,3] array, got {rotation!r}")
+    else:
+        R = _host_array(rotation, "rotation")
+        if R.shape not in ((3, 3), (S, 3, 3)):
+            raise ValueError(f"TrajectoryDataset: a rotation array must be [3,3] or [{S},3,3], got {list(R.shape)}")
+        R = np.broadcast_to(R, (S, 3, 3))
+    table = np.zeros((S, 12), dtype=np.float32)
+    table[:, :9] = R.reshape(S, 9)   # built in fp64, rounded once
+    if translation is not None:
+        if isinstance(translation, (np.ndarray, torch.Tensor)):   # values, applied as given
+            t = _host_array(translation, "translation")
+            if t.shape not in ((3,), (S, 3)):
+                raise ValueError(f"TrajectoryDataset: a translation array must be [3] or [{S},3], got {list(t.shape)}")
+            t = np.broadcast_to(t, (S, 3))
+        else:                                                     # a scale: python numbers
+            scale = _host_array(translation, "translation")
+            if scale.shape not in ((), (3,)):
+                raise ValueError(f"TrajectoryDataset: a translation scale must be a number or three, got {translation!r}")
+            t = rng.standard_normal((S, 3)) * scale
+        table[:, 9:] = t
+    return table, translation is not None
 
 
 class TrajectoryDataset:
@@ -913,9 +1016,22 @@ class TrajectoryDataset:
     tensors by three launches whatever the batch size (csrc/traj.hip), the graphs by the two batched calls of ``water3d_batch``,
     whose one read-back is the batch's only one.  ``vel_0`` and the copies are bit-equal to the per-sample path; ``node_feat[:,0]`` is
     ``sqrt((vx*vx + vy*vy) + vz*vz)`` with every operation rounded by itself, and ``loc_mean`` an fp64 sum in a fixed order rounded
-    once (include/fastegnn_hip.h) -- within a unit in the last place of torch's reductions, not bit-equal to them."""
+    once (include/fastegnn_hip.h) -- within a unit in the last place of torch's reductions, not bit-equal to them.
 
-    def __init__(self, trajectories, virtual_channels, delta_t, radius, cutoff_rate=0.0, samples="all", device="cuda"):
+    Rigid motions: the reference rotates and shifts its test partitions before it builds their graphs
+    (``datasets/simulation/dataset.py:71-77``, ``datasets/protein/dataset.py:131-142``).  ``rotation``: None, ``"y"`` (a rotation about
+    y by a whole number of degrees from [0, 360] per sample: ``random_rotate_y``), ``"xyz"`` (``random_rotate``: about x, then y, then
+    z) or an array / tensor ``[3,3]`` (every sample) or ``[S,3,3]`` (per sample), applied as given.  ``translation``: None, a SCALE
+    given as python numbers -- a float, or a tuple / list of three, one per axis: ``t = standard_normal(3) * scale`` per sample, the
+    reference's ``randn(3) * box / 2`` with ``scale = box / 2`` -- or an ARRAY / tensor ``[3]`` or ``[S,3]`` of values, applied as
+    given.  Non-finite or mis-shaped input raises ValueError.  The drawn forms use ``np.random.default_rng(motion_seed)``: the angles
+    of all samples first, then the translations.  ``ds.motion``: the table fp32 ``[S,12]`` (R row-major, then t) on the device, built
+    and uploaded once, or None.  With a table, ``batch`` / ``TrajectoryLoader`` / ``Rollout`` / ``ds[i]`` give the MOVED clouds
+    (``apply_motion``'s rule, applied inside the gather, before the graph build: four launches for the node side); without one, exactly
+    what they gave before."""
+
+    def __init__(self, trajectories, virtual_channels, delta_t, radius, cutoff_rate=0.0, samples="all", device="cuda", rotation=None,
+                 translation=None, motion_seed=0):
         self.virtual_channels, self.delta_t = int(virtual_channels), int(delta_t)
         self.radius, self.cutoff_rate, self.device = float(radius), float(cutoff_rate), torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:   # (so that a tensor's device compares equal to it)
@@ -973,14 +1089,20 @@ class TrajectoryDataset:
         self.samples_dev = torch.from_numpy(self.samples).to(self.device)
         self._node_cnt = self.n_host[t]
         self.frames = [(self.keys[int(a)], int(b)) for a, b in self.samples]
+        table, self._has_t = _motion_table(self.samples.shape[0], rotation, translation, motion_seed)
+        self.motion = None if table is None else torch.from_numpy(table).to(self.device)   # built once, uploaded once
 
     @classmethod
     def from_directory(cls, dataset_name, data_dir, virtual_channels, partition="train", max_samples=1e8, delta_t=15, cutoff_rate=0.0,
-                       device="cuda", seed=0, radius=None) -> "TrajectoryDataset":
+                       device="cuda", seed=0, radius=None, rotation=None, translation=None, motion_seed=0) -> "TrajectoryDataset":
         """The samples ``Simulation(dataset_name, data_dir, ..., seed=seed)`` draws, without building their graphs: the same
         ``read_trajectories`` pass and the same generator calls in the same order -- ``FRAMES_PER_TRAJECTORY`` start frames per
         trajectory from ``[0, min(250, T - 1 - max(1, delta_t))]``, cut at ``max_samples``, then one permutation -- so ``ds.frames``
-        equals ``Simulation(...).frames`` and ``ds[i]`` equals ``Simulation(...)[i]``."""
+        equals ``Simulation(...).frames`` and ``ds[i]`` equals ``Simulation(...)[i]``.  ``rotation`` / ``translation`` / ``motion_seed``
+        are the constructor's; ``rotation="reference"`` is the reference's protocol for these sets (``datasets/simulation/dataset.py:71-77``):
+        ``"y"`` for the ``test`` partition, none for the others."""
+        if isinstance(rotation, str) and rotation == "reference":
+            rotation = "y" if partition == "test" else None
         rng = np.random.default_rng(seed)
         delta_t, max_samples = int(delta_t), int(max_samples)
         trajectories, samples = [], []
@@ -994,7 +1116,8 @@ class TrajectoryDataset:
                 break
         order = rng.permutation(len(samples))
         samples = np.asarray(samples, dtype=np.int64).reshape(-1, 2)[order]
-        return cls(trajectories, virtual_channels, delta_t, Simulation.RADIUS if radius is None else radius, cutoff_rate, samples, device)
+        return cls(trajectories, virtual_channels, delta_t, Simulation.RADIUS if radius is None else radius, cutoff_rate, samples, device,
+                   rotation=rotation, translation=translation, motion_seed=motion_seed)
 
     def __len__(self) -> int:
         return self.samples.shape[0]
@@ -1007,12 +1130,45 @@ class TrajectoryDataset:
         t, f = (int(v) for v in self.samples[i % S])
         n, r0, k0 = int(self.n_host[t]), int(self.row0_host[t]), int(self.kind0_host[t])
         at = lambda frame: self.pos[r0 + frame * n:r0 + (frame + 1) * n]  # noqa: E731
-        return water3d_frame(at(f), at(f + 1) - at(f), at(f + self.delta_t), self.kind[k0:k0 + n], self.virtual_channels,
-                             self.radius, self.cutoff_rate)
+        loc_0, vel_0, loc_t = at(f), at(f + 1) - at(f), at(f + self.delta_t)
+        if self.motion is not None:   # the clouds ``batch`` sees: the same rule, restated in torch
+            R, t = self.motion[i % S, :9].view(3, 3), self.motion[i % S, 9:] if self._has_t else None
+            loc_0, vel_0, loc_t = apply_motion(loc_0, R, t), apply_motion(vel_0, R), apply_motion(loc_t, R, t)
+        return water3d_frame(loc_0, vel_0, loc_t, self.kind[k0:k0 + n], self.virtual_channels, self.radius, self.cutoff_rate)
 
-    def _assemble_nodes(self, ids_dev: torch.Tensor, ids_host: np.ndarray) -> dict:
+    def _motion_rows(self, ids_dev: torch.Tensor, motion):
+        """(device fp32 [B,12], has_t) of the batch ``ids_dev`` -- the rows of the dataset's table (one ``index_select`` on the device,
+        nothing uploaded) or ``batch``'s explicit ``motion`` -- or (None, False) for an unmoved batch"""
+        B = ids_dev.numel()
+        if motion is None:
+            return (None, False) if self.motion is None else (self.motion.index_select(0, ids_dev), self._has_t)
+        who = "TrajectoryDataset.batch: motion"
+        if isinstance(motion, (tuple, list)):
+            if len(motion) != 2:
+                raise ValueError(f"{who} must be a [B,12] tensor or a pair (R [B,3,3], t [B,3] or None)")
+            R, t = motion
+            R = torch.as_tensor(R).to(self.device, torch.float32)
+            if tuple(R.shape) != (B, 3, 3):
+                raise ValueError(f"{who}: R must be [{B},3,3], got {list(R.shape)}")
+            has_t = t is not None
+            t = torch.as_tensor(t).to(self.device, torch.float32) if has_t else torch.zeros((B, 3), dtype=torch.float32, device=self.device)
+            if tuple(t.shape) != (B, 3):
+                raise ValueError(f"{who}: t must be [{B},3], got {list(t.shape)}")
+            rows = torch.cat([R.reshape(B, 9), t], 1)
+        else:
+            rows, has_t = torch.as_tensor(motion), True
+            if tuple(rows.shape) != (B, 12) or rows.dtype != torch.float32:
+                raise ValueError(f"{who} must be fp32 [{B},12] (R row-major, then t), got {rows.dtype} {list(rows.shape)}")
+            rows = rows.to(self.device)   # (a tensor already there is used where it is)
+        if not bool(torch.isfinite(rows).all()):   # (one read-back for a device tensor: non-finite positions must not reach the graph build)
+            raise ValueError(f"{who} must be finite")
+        return rows.contiguous(), has_t
+
+    def _assemble_nodes(self, ids_dev: torch.Tensor, ids_host: np.ndarray, motion=None) -> dict:
         """the node side of the batch of the samples ``ids_dev`` (device int64 [B]; ``ids_host``: the same on the host, already
-        validated): three device calls, sizes from the host's node counts, nothing uploaded or read back"""
+        validated): three device calls, sizes from the host's node counts, nothing uploaded or read back.  A moved batch (the
+        dataset's table, or ``motion`` as ``batch`` takes it) is four: plan, the selection of the motion rows, the moved gather, the
+        mean of the moved ``loc_0``; its dict also holds ``"motion"`` = (the rows fp32 [B,12], has_t)."""
         B, dev, C = int(ids_host.size), self.device, self.virtual_channels
         N = int(self._node_cnt[ids_host].sum())
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
@@ -1022,23 +1178,32 @@ class TrajectoryDataset:
         slots = torch.empty((B, _TRAJ_SLOT_WORDS), dtype=torch.int64, device=dev)
         ops = _TRAJ_OPS
         ops.plan(ids_dev, self.samples_dev, self.row0, self.n, self.T, self.kind0, self.delta_t, out["ptr"], slots)
-        ops.gather(out["ptr"], slots, N, self.pos, self.kind, self.kind_scaled, *[out[k] for k in _NODE_KEYS], out["batch"])
-        ops.mean(out["ptr"], slots, self.pos, out["loc_mean"])
+        rows, has_t = self._motion_rows(ids_dev, motion)
+        if rows is None:
+            ops.gather(out["ptr"], slots, N, self.pos, self.kind, self.kind_scaled, *[out[k] for k in _NODE_KEYS], out["batch"])
+            ops.mean(out["ptr"], slots, self.pos, out["loc_mean"])
+        else:
+            ops.gather_moved(out["ptr"], slots, N, self.pos, self.kind, self.kind_scaled, *[out[k] for k in _NODE_KEYS], out["batch"],
+                             rows, has_t)
+            ops.mean_of(out["ptr"], out["loc_0"], out["loc_mean"])
+            out["motion"] = (rows, has_t)
         return out
 
-    def _assemble(self, ids_dev: torch.Tensor, ids_host: np.ndarray) -> Batch:
-        out = self._assemble_nodes(ids_dev, ids_host)
+    def _assemble(self, ids_dev: torch.Tensor, ids_host: np.ndarray, motion=None) -> Batch:
+        out = self._assemble_nodes(ids_dev, ids_host, motion)
         ptr_host = [0] + np.cumsum(self._node_cnt[ids_host]).tolist()
         ei, dist = _TRAJ_OPS.edges(out["loc_0"], out["ptr"], ptr_host, self.radius, self.cutoff_rate)
         out["edge_attr"], out["edge_index"] = dist.unsqueeze(-1), ei
         return Batch(**{k: out[k] for k in _BATCH_KEYS})
 
-    def batch(self, ids) -> Batch:
+    def batch(self, ids, motion=None) -> Batch:
         """The ``Batch`` of the samples ``ids``: a sequence of ints, a numpy array, or an int64 tensor on either side, with values in
         ``[0, len(self))`` (any order, repeats allowed), checked on the host as ``PackedDataset.batch`` does -- an id outside raises
         IndexError.  Host ids are uploaded through pinned memory; a device tensor is used where it is, and checking it costs one
-        read-back (``TrajectoryLoader`` keeps both copies and pays neither)."""
-        return self._assemble(*self._checked_ids(ids))
+        read-back (``TrajectoryLoader`` keeps both copies and pays neither).  ``motion`` overrides the dataset's motion table for this
+        call: fp32 ``[B,12]`` (per slot R row-major, then t) or a pair ``(R [B,3,3], t [B,3] or None)``, on either device, finite
+        (checked: one read-back when it lives on the device)."""
+        return self._assemble(*self._checked_ids(ids), motion)
 
     def _checked_ids(self, ids, who: str = "TrajectoryDataset.batch"):
         """``batch``'s validation of ``ids`` -> (the ids on the device, the same as a host int64 array)"""

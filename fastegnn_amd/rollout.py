@@ -24,7 +24,8 @@ _NO_CPU_ROLLOUT = "fastegnn_amd: a rollout needs device-resident state (there is
 
 class HipRolloutOps:
     """The device calls of a rollout on libfastegnn_hip.so (the product path): ``plan``, ``advance`` and ``graph`` are the launches of
-    csrc/rollout.hip (include/fastegnn_hip.h, fastegnn_rollout_*), ``augment`` is ``train.augment_edge_attr``.  tests/rollout_ref.py
+    csrc/rollout.hip (include/fastegnn_hip.h, fastegnn_rollout_*), ``graph_moved`` is ``graph`` for a dataset with rigid motions
+    (its truth rows are moved first), ``augment`` is ``train.augment_edge_attr``.  tests/rollout_ref.py
     restates them in torch, so that tests/test_rollout_cpu.py can drive the orchestration without a GPU (the ``HipTrajOps`` precedent)."""
 
     @staticmethod
@@ -62,6 +63,23 @@ class HipRolloutOps:
                                                K.ptr(pos) if score else None, pos.size(0) if score else 0,
                                                K.ptr(truth_rows) if score else None, loc_mean.size(2), K.ptr(loc_mean), K.ptr(sse),
                                                _stream(ptr.device)), "fastegnn_rollout_graph")
+
+    @staticmethod
+    def graph_moved(ptr, loc, x_new, pos, truth_rows, loc_mean, sse, motion, has_t) -> None:
+        """``graph`` with a score against MOVED truth: graph b's truth rows are moved by ``motion[b]`` (fp32 [B,12]: R row-major, then
+        t; ``has_t`` false: no translation is added) in fp32 by the rule of ``data.apply_motion`` before the fp64 difference"""
+        if not ptr.is_cuda:
+            raise RuntimeError(_NO_CPU_ROLLOUT)
+        B = ptr.numel() - 1
+        if not (motion.is_cuda and motion.dtype == torch.float32 and tuple(motion.shape) == (B, 12) and motion.is_contiguous()):
+            raise ValueError(f"fastegnn_amd: the motion rows of a rollout of {B} samples must be a contiguous device fp32 [{B},12] tensor")
+        from . import _lib as K
+        from .model import _stream
+        score = sse is not None
+        K.check(K.lib().fastegnn_rollout_graph_moved(K.ptr(ptr), B, K.ptr(loc), K.ptr(x_new) if score else None, loc.size(0),
+                                                     K.ptr(pos) if score else None, pos.size(0) if score else 0,
+                                                     K.ptr(truth_rows) if score else None, loc_mean.size(2), K.ptr(loc_mean), K.ptr(sse),
+                                                     K.ptr(motion), int(bool(has_t)), _stream(ptr.device)), "fastegnn_rollout_graph_moved")
 
     @staticmethod
     def augment(edge_attr, loc_0, edge_index):
@@ -114,11 +132,14 @@ class Rollout:
     """``steps`` steps of ``model`` on the samples ``ids`` of the ``TrajectoryDataset`` ``ds`` (stride ``ds.delta_t`` >= 1, else
     ValueError), each prediction fed back as the next input.  ``ids`` are validated like ``TrajectoryDataset.batch``'s.
 
-    * Step 0 gets exactly the node tensors and the graph of ``ds.batch(ids)``.
+    * Step 0 gets exactly the node tensors and the graph of ``ds.batch(ids)``.  On a dataset with a motion table (``rotation=`` /
+      ``translation=``) that batch is moved, and so is the whole rollout: the truth rows are moved by each slot's motion
+      (``data.apply_motion``'s rule, in fp32) before the difference, so ``pred`` and ``per_graph`` are in the moved frame.
     * After step k the model has returned ``x_new``, its prediction of frame ``f + (k+1) delta_t``; then ``vel = (x_new - loc) *
       (1/delta_t)`` (one fp32 subtraction, one fp32 multiplication by the fp32 value ``1.0f/delta_t``), ``node_feat[:,0] = |vel|`` by the
       loader's rule, ``loc = x_new``, ``loc_mean`` by the loader's rule; ``node_feat[:,1]``, ``node_attr``, ``ptr``, ``batch`` stay.
-    * ``sse[k,b]`` = the fp64 sum over cloud b's nodes and components of ``(x_new - pos[f + (k+1) delta_t])**2``, NaN where the
+    * ``sse[k,b]`` = the fp64 sum over cloud b's nodes and components of ``(x_new - pos[f + (k+1) delta_t])**2`` (the moved rows of
+      ``pos`` on a moved dataset), NaN where the
       trajectory has no such frame; the per-graph MSE is ``sse / (3 n_b)``.
     * A non-finite component of ``x_new`` never reaches the graph build: the state keeps the old position there, with velocity 0; the
       flag is read after the next graph build's read-back and the rollout stops with ``stopped = ("non-finite", k)``, k the step that
@@ -130,7 +151,7 @@ class Rollout:
     ``.batch``: the ``Batch`` the next ``step()`` feeds the model -- collate's keys without ``loc_t``; valid until the next ``step()``
     (the state tensors are updated in place), None once the rollout has ended.  ``.step()`` -> the prediction [N,3].  ``.k``: steps
     taken.  ``.result()``: see there.  State and score buffers are allocated here, once; a step allocates what the model and the graph
-    build allocate.  One device; a step is not capturable as a whole (the graph build reads its edge counts back); no rotation."""
+    build allocate.  One device; a step is not capturable as a whole (the graph build reads its edge counts back)."""
 
     def __init__(self, model, ds, ids, *, steps, record=False, max_edges=None):
         if not isinstance(ds, D.TrajectoryDataset):
@@ -142,6 +163,7 @@ class Rollout:
         nodes = ds._assemble_nodes(ids_dev, ids_host)
         node_cnt = ds._node_cnt[ids_host]
         self._ds = ds
+        self._motion = nodes.get("motion")   # None, or (the slots' motion rows [B,12], has_t)
         self._setup(model, {k: nodes[k] for k in ("loc_0", "vel_0", "node_feat", "node_attr", "loc_mean", "batch", "ptr")},
                     [0] + np.cumsum(node_cnt).tolist(), ds.radius, ds.cutoff_rate, ds.delta_t, steps, record, max_edges)
         B = len(ids_host)
@@ -177,7 +199,7 @@ class Rollout:
                  "batch": torch.repeat_interleave(torch.arange(B, dtype=torch.int64), counts).to(dev),
                  "ptr": torch.tensor(ptr_host, dtype=torch.int64).to(dev)}
         self = cls.__new__(cls)
-        self._ds = None
+        self._ds = self._motion = None
         self._setup(model, state, ptr_host, float(radius), float(cutoff_rate), delta_t, steps, record, max_edges)
         self._truth = self._sse = self._has_truth = None
         _ROLLOUT_OPS.graph(state["ptr"], state["loc_0"], None, None, None, state["loc_mean"], None)
@@ -236,8 +258,11 @@ class Rollout:
             ops.advance(x_new, self._delta_t, s["loc_0"], s["vel_0"], s["node_feat"], self._pred[k] if self._pred is not None else None,
                         self._flag)
             score = self._sse is not None
-            ops.graph(s["ptr"], s["loc_0"], x_new if score else None, self._ds.pos if score else None,
-                      self._truth[k] if score else None, s["loc_mean"], self._sse[k] if score else None)
+            if score and self._motion is not None:
+                ops.graph_moved(s["ptr"], s["loc_0"], x_new, self._ds.pos, self._truth[k], s["loc_mean"], self._sse[k], *self._motion)
+            else:
+                ops.graph(s["ptr"], s["loc_0"], x_new if score else None, self._ds.pos if score else None,
+                          self._truth[k] if score else None, s["loc_mean"], self._sse[k] if score else None)
             self.k = k + 1
             if self.k < self.steps:
                 self._build_graph()          # (its read-back: the advance launch has run, the flag word is current)

@@ -813,6 +813,37 @@ int fastegnn_rollout_advance(const float *x_new, int64_t n_nodes, int32_t delta_
 int fastegnn_rollout_graph(const int64_t *ptr, int32_t B, const float *loc, const float *x_new, int64_t n_nodes, const float *pos,
                            int64_t pos_rows, const int64_t *truth_rows, int32_t C, float *loc_mean, double *sse, void *stream);
 
+/* ---- rigid motions: trajectory batches and rollouts in a rotated and shifted frame (datasets/simulation/dataset.py:71-77,
+ *      datasets/protein/dataset.py:131-142: the reference moves its test partitions BEFORE it builds their graphs) ----
+ * ADDITIVE exports, found by symbol: FASTEGNN_ABI_VERSION stays 108.
+ * THE RULE.  A motion is 12 fp32 values: R row-major (9), then t (3).  For a row vector p
+ *     q[j] = ((p[0]*R[0][j] + p[1]*R[1][j]) + p[2]*R[2][j])        j = 0, 1, 2
+ *     moved position = q + t          moved velocity = q  (no t)
+ * Every multiplication and every addition is fp32 and rounded by itself (no fused multiply-add: the statements are compiled with
+ * contraction off, as _gather's speed is): the reference's x @ R (+ t) in one fixed evaluation order, which elementwise torch
+ * operations reproduce bit for bit on either device (fastegnn_amd.data.apply_motion).  With has_t == 0 the `+ t` is NOT executed -- it
+ * is not an addition of +0.0f, which would turn -0.0 into +0.0 -- and the three t values are not used.
+ * `motion` is fp32 [B,12] on the device, one row per SLOT of the batch (row i moves the cloud of ids[i]); it is read at the slot index,
+ * which is below B by construction, never through an index that comes from the data.
+ *   _traj_gather_moved   fastegnn_traj_gather with the motion applied in the same launch (same tiling; a tile inside one slot loads
+ *                        its 12 values once): loc_0 = move(pos[f]), loc_t = move(pos[f+delta_t]), vel_0 = rotate(pos[f+1] - pos[f]) --
+ *                        the difference first, as the reference has it --, node_feat[:,0] = the speed of the ROTATED velocity by
+ *                        _gather's rule; node_feat[:,1], node_attr and batch_out as _gather writes them; the same clamps and skips.
+ *                        loc_mean of a moved batch is _mean's rule over the moved loc_0, which fastegnn_rollout_graph(ptr, B, loc_0,
+ *                        NULL, n, NULL, 0, NULL, C, loc_mean, NULL, stream) computes from the [n,3] tensor: four launches whatever B.
+ *   _rollout_graph_moved fastegnn_rollout_graph with the truth row moved, in fp32 by the rule, before the fp64 difference:
+ *                        d = (double)x_new - (double)move(pos[truth_rows[b] + i]); the summation order, the NaN rules and loc_mean
+ *                        are _rollout_graph's (loc_mean has the bits of the unmoved call on the same `loc`).  sse null: motion is
+ *                        not read.
+ * FASTEGNN_E_INVALID before any launch for what _traj_gather / _rollout_graph refuse, and for a null `motion` that would be read. */
+int fastegnn_traj_gather_moved(const int64_t *ptr, const int64_t *slots, int32_t B, int64_t n_nodes_out, const float *pos,
+                               int64_t pos_rows, const float *kind, const float *kind_scaled, int64_t kind_rows, float *loc_0,
+                               float *loc_t, float *vel_0, float *node_feat, float *node_attr, int64_t *batch_out, const float *motion,
+                               int32_t has_t, void *stream);
+int fastegnn_rollout_graph_moved(const int64_t *ptr, int32_t B, const float *loc, const float *x_new, int64_t n_nodes, const float *pos,
+                                 int64_t pos_rows, const int64_t *truth_rows, int32_t C, float *loc_mean, double *sse,
+                                 const float *motion, int32_t has_t, void *stream);
+
 /* ---- exchange steps of the sharded path (the reference has no distributed code) ----
  * RCCL collectives behind the C ABI: every call is enqueued on `stream` (ordered with the stage kernels, capturable
  * into a HIP graph) and returns at once.  RCCL is bound at run time (dlopen; FASTEGNN_E_NODEVICE when absent).
