@@ -909,10 +909,12 @@ __device__ __forceinline__ Split2s vsplit2_scaled(const Vec &v) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(v.t[t][r]));
   m = qmax(m);
-  // m in [2^(e-127), 2^(e-126)): scale 2^(141-e) puts it into [2^14, 2^15).  Exponent fields clamped to the normal range: items
-  // whose largest component is below 2^-113 (or zero) get inv = 0 -- their product is dropped, it is below fp32's range anyway.
+  // m in [2^(e-127), 2^(e-126)): scale 2^(141-e) puts it into [2^14, 2^15).  Exponent fields clamped so that the scale AND its
+  // inverse are normal numbers: an item whose largest component is below 2^-112 takes the scale 2^126 (inv = 2^-126) and lands in
+  // [1, 2^14) -- two 11-bit parts of it are still exact to 2^-22 of the item.  (Until the magnitude tests the clamp was 254, whose inverse
+  // has exponent field 0: inv = 0, and the product of every item below 2^-113 -- far inside fp32's range -- was dropped.)
   int se = 268 - (int)(f2u(m) >> 23);
-  se = se > 254 ? 254 : (se < 1 ? 1 : se);
+  se = se > 253 ? 253 : (se < 1 ? 1 : se);
   const float sc = __builtin_bit_cast(float, (unsigned)se << 23);
   Split2s S;
   S.inv = __builtin_bit_cast(float, (unsigned)(254 - se) << 23);
@@ -1109,10 +1111,13 @@ struct WgScale {
     const int em = __builtin_amdgcn_readfirstlane((int)(f2u(m) >> 23));   // biased exponent; 0 for a zero (or subnormal) tile
     if (em == 0 || em == 255) return 1.f;                                 // nothing to scale; Inf / NaN tiles poison the sum as in fp32
     int want = 268 - em;                                                  // m S in [2^14, 2^15)
-    want = want > 254 ? 254 : (want < 1 ? 1 : want);
+    want = want > 253 ? 253 : (want < 1 ? 1 : want);                      // (253: inv() stays a normal number, as in vsplit2_scaled)
     if (se == 0) { se = want; return 1.f; }
     if (want >= se) return 1.f;                                           // the tile fits under the current scale
-    const float f = __builtin_bit_cast(float, (unsigned)(127 - (se - want)) << 23);   // 2^(want - se) < 1
+    // 2^(want - se) < 1.  se and want lie in [14, 253]: a drop of 127 binades or more has no normal power of two (the exponent field
+    // would wrap into the sign bit: -2^126 for a drop of 130) -- the old sum is below the resolution of the new scale, the factor is 0
+    const int drop = se - want;
+    const float f = drop >= 127 ? 0.f : __builtin_bit_cast(float, (unsigned)(127 - drop) << 23);
     se = want;
     return f;
   }

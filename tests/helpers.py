@@ -210,6 +210,19 @@ GRAD_EXCEPTIONS = [
      "against the CPU's 1.0e-7 / 1.4e-7 / 1.9e-7 (681 rows).  Worst: 1.579e-6 vs ref 2.69e-7 (681 nodes, all flags) and 1.557e-6 vs ref 2.02e-7 (64 nodes, "
      "gravity) = 1.04e-6 / 1.15e-6 over 2 x ref; bit-identical over four runs and on all four libraries (the kernel is the bf16x3 form in each); without "
      "gravity (four products) 1.04e-6 vs 2.60e-7: inside the plain rule"),
+    # The magnitude cases of the stage level (tests/test_gpu_stage_magnitudes.py, tests/test_stage_magnitudes_cpu.py: case names carry ":mag-<profile>",
+    # which no other case does).  20 280 comparisons per pass over the four libraries, whole buffers and row groups; two kinds beyond the plain rule
+    (r"^stage:node_pre_backward:.*:mag-", r"^g_h\[", 2.0, 1.7e-6,
+     "the entry for g_h above, on the row groups of a magnitude case (a group's name is 'g_h[<group>]', which '^g_h$' does not match): the start value is "
+     "scaled with the rows, so every group pays the same price for adding five chained products into it.  FASTEGNN_TOL_DUMP, 681 nodes, all flags, "
+     "bit-identical on all four libraries: g_h[g0] 1.579e-6 vs ref 2.69e-7 under g_ramp_up / g_ramp_down / g_far (= the whole-tensor figure above: graph 0 "
+     "holds the worst row), g_h[rows0] 1.677e-6 vs ref 2.55e-7 under g_rows = 1.04e-6 / 1.17e-6 over 2 x ref; floor 1.7e-6 <= 1.5 x 1.17e-6, the floor of the "
+     "entry above.  The groups of the 64- and 65-node shapes are inside the plain rule"),
+    (r":mag-g_rows:", r"^grad\.(gravity_mlp|coord_mlp_vel)\.2\.bias$", 2.0, 5.0e-6,
+     "the scalar head biases under g_rows: ONE number, the sum of N per-node terms of which the ~N/5 rows scaled by 2^20 carry everything -- 13 terms on the "
+     "64-node shape, which cancel.  The clean fp32 CPU statement with its nodes in another order (tests/test_stage_magnitudes_cpu.py, the second association) "
+     "measures 9.35e-6 against the first association's 2.98e-6 on grad.coord_mlp_vel.2.bias = 3.39e-6 over 2 x ref; floor 5.0e-6 <= 1.5 x 3.39e-6.  The HIP "
+     "libraries are far inside on this tensor: FASTEGNN_TOL_DUMP, worst 0.07 of the tolerance it had without this entry (681 nodes, hip_act)"),
 ]
 
 

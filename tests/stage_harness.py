@@ -104,6 +104,9 @@ class Case:
     key: tuple = ()                           # the arguments of make_case
     wiring: tuple = ("fastegnn",)
     act: tuple = ("silu", 0.0)
+    magnitude: str = "unit"                   # the magnitude profile (MAGNITUDES below)
+    row_exp: Optional[torch.Tensor] = None    # int64 [N]: the power of two the profile put on each row; None for "unit"
+    graph_exp: Optional[torch.Tensor] = None  # int64 [B]: the same per graph
 
 
 # --------------------------------------------------------------------------
@@ -234,9 +237,11 @@ def _egnn_operand_edges(cfg, t, ei, n_src, row_begin, g):
 
 @functools.lru_cache(maxsize=None)
 def make_case(sizes: Tuple[int, ...], C: int, ea: int, na: int, flags: Tuple[str, ...], graph_kind: str = "random",
-              seed: int = 0, wiring: tuple = FASTEGNN_WIRING, act: tuple = SILU) -> Case:
+              seed: int = 0, wiring: tuple = FASTEGNN_WIRING, act: tuple = SILU, magnitude: str = "unit") -> Case:
     from fastegnn_amd._lib import PARAM_SLOTS
     sizes, flags = tuple(sizes), tuple(flags)
+    if magnitude != "unit":
+        return _with_magnitude(make_case(sizes, C, ea, na, flags, graph_kind, seed, wiring, act), magnitude)
     cfg = config(C, ea, na, flags, wiring, act)
     N, B = sum(sizes), len(sizes)
     sub = graph_kind == "subrange"
@@ -283,6 +288,96 @@ def make_case(sizes: Tuple[int, ...], C: int, ea: int, na: int, flags: Tuple[str
                     key=(sizes, C, ea, na, flags, graph_kind, seed, wiring, act), wiring=wiring, act=act)
     return Case(name, cfg, flags, sizes, N, B, C, n_src, row_begin, graph_kind, params, grads0, ei, batch, t,
                 key=(sizes, C, ea, na, flags, graph_kind, seed))
+
+
+# --------------------------------------------------------------------------
+# magnitude profiles: the finished unit draw, rescaled in place by exact powers of two (make_case(..., magnitude=...)).
+# The default build splits every gradient operand relative to a power-of-two scale -- per 64-value item (csrc/common.h: vsplit2_scaled)
+# or per operand stream of a weight-gradient consumer (WgScale) -- and a plain randn draw gives every item and every ticket the SAME
+# scale: a scale taken from the wrong lanes, a stream scale that is never lowered, an inverse applied before a lowering all compute the
+# right number there.  Under a profile the rows of one tensor differ by 2^12 .. 2^130.
+#   backward profiles scale the upstream gradients (G_NODE / G_GRAPH / G_EDGE: every g_* operand and the start values of what the ABI
+#   accumulates); the backward is linear in them and the graphs of a batch are independent, so the truth of every graph-local output of
+#   a per-graph profile is exactly 2^s_b times the unit case's (tests/test_stage_magnitudes_cpu.py);
+#   the forward profile scales the feature operands (F_NODE / F_GRAPH and the Q block of QX_src) mildly; nothing is linear there.
+# Parameters, coordinates, velocities, attributes and the start values of the PARAMETER gradients are never scaled.
+# --------------------------------------------------------------------------
+MAG_GRAPH = {"g_ramp_up": (-12, 0, 12), "g_ramp_down": (12, 0, -12), "g_far": (-100, 0, 30), "f_ramp": (-6, 0, 3)}   # s_b, cyclic in graph order
+BACKWARD_PROFILES, FORWARD_PROFILES = ("g_ramp_up", "g_ramp_down", "g_rows", "g_far"), ("f_ramp",)
+MAGNITUDES = BACKWARD_PROFILES + FORWARD_PROFILES
+ROWS_UP, ROWS_DOWN = 20, -20               # g_rows: rows 0 and 15 of every 16-row tile and the last row of every graph; row 7 of every tile
+G_NODE = ("g_h_out", "g_x_out", "g_aggm", "g_aggx", "g_P", "g_A", "g_svel", "g_sgrav", "g_QX", "g_xrow", "g_vel0", "g_h0", "g_x0", "g_na0")
+G_GRAPH = ("g_Z_out", "g_HvT_out", "g_poolV", "g_poolX", "g_Bc", "g_Zp", "g_xbar", "g_HvT0", "g_Z0")
+G_EDGE = ("g_ea0",)                        # rows in sorted-edge order (run_stage hands it over as g_ea_sorted)
+F_NODE, F_GRAPH = ("h", "P", "A", "aggm"), ("Bc", "HvT")
+
+
+def _sorted_rows(case) -> torch.Tensor:
+    """local row of every edge in sorted-edge order (the order of g_ea_sorted: a stable sort by row)"""
+    return torch.sort(case.edge_index[0] - case.row_begin, stable=True).values
+
+
+def _with_magnitude(unit: Case, profile: str) -> Case:
+    assert profile in MAGNITUDES, profile
+    assert unit.n_src == unit.N and unit.row_begin == 0 and unit.graph_kind != "two_launch", "magnitude profiles: whole-table graphs only"
+    N, B = unit.N, unit.B
+    if profile == "g_rows":
+        i = torch.arange(N)
+        last = torch.tensor([sum(unit.sizes[:b + 1]) - 1 for b in range(B) if unit.sizes[b] > 0], dtype=torch.long)
+        row_exp = torch.zeros(N, dtype=torch.long)
+        row_exp[i % 16 == 7] = ROWS_DOWN
+        row_exp[(i % 16 == 0) | (i % 16 == 15)] = ROWS_UP
+        row_exp[last] = ROWS_UP
+        graph_exp = torch.zeros(B, dtype=torch.long)
+    else:
+        if profile == "g_far":
+            assert B >= 3, "g_far: at least three graphs"
+        s = MAG_GRAPH[profile]
+        graph_exp = torch.tensor([s[b % 3] for b in range(B)], dtype=torch.long)
+        row_exp = graph_exp[unit.batch]
+    t = {k: v.clone() for k, v in unit.t.items()}
+
+    def scale(k, e):
+        v = t[k]
+        t[k] = v * torch.exp2(e.double()).view(-1, *([1] * (v.dim() - 1)))
+
+    if profile in BACKWARD_PROFILES:
+        assert {k for k in t if k.startswith("g_")} == set(G_NODE + G_GRAPH + G_EDGE)
+        for k in G_NODE:
+            scale(k, row_exp)
+        for k in G_GRAPH:
+            scale(k, graph_exp)
+        E = unit.edge_index.size(1)
+        edge_exp = torch.zeros(t["g_ea0"].size(0), dtype=torch.long)
+        edge_exp[:E] = row_exp[_sorted_rows(unit)]
+        scale("g_ea0", edge_exp)
+    else:
+        for k in F_NODE:
+            scale(k, row_exp)
+        for k in F_GRAPH:
+            scale(k, graph_exp)
+        q = t["QX_src"][:, :H].clone()
+        t["QX_src"][:, :H] = q * torch.exp2(row_exp.double()).view(-1, 1)      # (the x columns, and t["x"] with them, stay)
+    for k, v in t.items():
+        if not torch.equal(v, unit.t[k]):
+            assert torch.equal(v, v.float().double()) and bool(torch.isfinite(v).all()), f"{profile}: {k} is not exact in fp32"
+    key = unit.key + ((0,) if len(unit.key) == 6 else ())
+    key = key + ((unit.wiring, unit.act) if len(key) == 7 else ()) + (profile,)
+    return dataclasses.replace(unit, name=f"{unit.name}:mag-{profile}", t=t, key=key, magnitude=profile, row_exp=row_exp, graph_exp=graph_exp)
+
+
+def groups_of(case: Case):
+    """-> None for a unit case; otherwise the row groups a magnitude case is compared by, as {"node": [(label, rows)], "edge": [(label,
+    sorted-edge indices)]}: the rows of every graph and, for g_rows, the three row classes -- so that a slice 12 .. 130 binades under
+    the tensor's maximum is held to its OWN magnitude.  An edge belongs to the group of its row."""
+    if case.magnitude == "unit":
+        return None
+    sets = [(f"g{b}", case.batch == b) for b in range(case.B)]
+    if case.magnitude == "g_rows":
+        sets += [("rows+20", case.row_exp == ROWS_UP), ("rows-20", case.row_exp == ROWS_DOWN), ("rows0", case.row_exp == 0)]
+    erow = _sorted_rows(case)
+    return {"node": [(lab, torch.nonzero(m).view(-1)) for lab, m in sets],
+            "edge": [(lab, torch.nonzero(m[erow]).view(-1)) for lab, m in sets]}
 
 
 def wiring_tag(wiring: tuple, act: tuple) -> str:
@@ -637,7 +732,10 @@ def run_stage(rn, name: str, case: Case, null: bool = False, want: bool = True, 
             # rounding of every atomic that lands in it: a start value of another magnitude would measure that, not the kernel)
             base = reference(name, case.key, (), scale)[1]["g_QX_src"]
             deal = torch.randperm(case.n_src, generator=torch.Generator().manual_seed(7))
-            acc("g_QX_src", base[deal].float().double())
+            start = base[deal]
+            if case.row_exp is not None:           # a magnitude case: every row starts at the magnitude of its OWN sums (an exact factor)
+                start = start * torch.exp2((case.row_exp - case.row_exp[deal]).double()).view(-1, 1)
+            acc("g_QX_src", start.float().double())
         else:
             out("g_QX_src", case.n_src, QX_LD)
         if rn.hip:
@@ -760,11 +858,14 @@ def _check(case, key, got, ref32, truth, bad, bf16):
 
 
 def compare(case: str, got: Dict[str, torch.Tensor], ref32: Dict[str, torch.Tensor], truth64: Dict[str, torch.Tensor],
-            sizes=None, bf16: bool = False) -> List[str]:
+            sizes=None, bf16: bool = False, groups=None) -> List[str]:
     """-> the comparisons of `got` that are further from `truth64` than the project's rule allows (tests.helpers.grad_check;
     the bf16 mode's own rule with bf16=True).  Every key of truth64 must be in got: a missing output is reported.  A parameter
-    gradient the stage must leave alone ("grad.<slot>" whose truth is zero everywhere) must be exactly its start value."""
+    gradient the stage must leave alone ("grad.<slot>" whose truth is zero everywhere) must be exactly its start value.
+    groups (groups_of(case), a magnitude case): every node- and edge-level buffer is ALSO compared on the rows of each group."""
     bad: List[str] = []
+    n_node = sum(sizes) if sizes is not None else None
+    assert groups is None or sizes is not None
     ptr = None
     if sizes is not None:
         ptr = [0]
@@ -795,6 +896,19 @@ def compare(case: str, got: Dict[str, torch.Tensor], ref32: Dict[str, torch.Tens
                 _check(case, f"{k}[g{i}]", g[i], r[i], tr[i], bad, bf16)
         else:
             _check(case, k, g, r, tr, bad, bf16)
+        if groups is not None and not k.startswith("grad.") and k != "xsum" and k not in PER_GRAPH and tr.dim() >= 1:
+            # a magnitude case: the rows of each group on their own as well, under the same rule -- the tolerance of a slice is set by
+            # the fp32 CPU evaluation's error on THAT slice (weight gradients and other sums over all rows stay whole-tensor comparisons)
+            level = "edge" if k.startswith("g_ea_sorted") else "node"
+            if level == "node" and tr.size(0) != n_node:
+                bad.append(f"{k}: {tr.size(0)} rows: neither a node-level nor an edge-level buffer of a magnitude case")
+                continue
+            for lab, idx in groups[level]:
+                if k in MIXED_QX:
+                    _check(case, f"{k}:Q[{lab}]", g[idx, :H], r[idx, :H], tr[idx, :H], bad, bf16)
+                    _check(case, f"{k}:x[{lab}]", g[idx, H:H + 3], r[idx, H:H + 3], tr[idx, H:H + 3], bad, bf16)
+                else:
+                    _check(case, f"{k}[{lab}]", g[idx], r[idx], tr[idx], bad, bf16)
     return bad
 
 
@@ -986,3 +1100,40 @@ def act_sibling_cases(stage: str):
 
 def wiring_case_id(key, variant) -> str:
     return variant_id(key[:6], variant) + "-" + wiring_tag(key[7], key[8]) + (f"-s{key[6]}" if key[6] else "")
+
+
+# --------------------------------------------------------------------------
+# the magnitude cases (tests/test_gpu_stage_magnitudes.py): the smallest shapes with more than one ticket per weight-gradient consumer and
+# ragged tiles.  A key is the full argument tuple of make_case, the profile last
+# --------------------------------------------------------------------------
+_PER_GRAPH_PROFILES = ("g_ramp_up", "g_ramp_down", "g_rows", "g_far", "f_ramp")
+MAG_SHAPES = [       # (shape, wiring, profiles)
+    ((S_RAGGED, 3, 2, 1, ALL_FLAGS, "random"), FASTEGNN_WIRING, _PER_GRAPH_PROFILES),
+    ((S_MANY, 16, 2, 0, ALL_FLAGS, "random"), FASTEGNN_WIRING, _PER_GRAPH_PROFILES),
+    ((S_65, 5, 7, 0, ALL_FLAGS, "deg32_33"), FASTEGNN_WIRING, ("g_rows", "f_ramp")),          # one graph
+    ((S_RAGGED, 3, 2, 0, ALL_FLAGS, "random"), RF, _PER_GRAPH_PROFILES),
+    (((65,), 0, 7, 0, (), "random"), ("egnn", True, False), ("g_rows",)),
+    ((S_RAGGED, 3, 2, 1, ("bf16",), "random"), FASTEGNN_WIRING, ("g_ramp_up",)),
+]
+
+
+def magnitude_keys(stage: str):
+    """the make_case keys of one stage: backward profiles on the backward stages (g_rows scales no per-graph operand: not on the per-graph
+    stages, which it leaves as they are), the forward profile on the forward stages"""
+    out = []
+    for sh, wiring, profiles in MAG_SHAPES:
+        if wiring[0] == "egnn" and stage not in EGNN_STAGES:
+            continue
+        for p in profiles:
+            if (stage in BACKWARD) != (p in BACKWARD_PROFILES) or (p == "g_rows" and stage in GRAPH_LEVEL):
+                continue
+            out.append(sh + (0, wiring, SILU, p))
+    return out
+
+
+def magnitude_cases(stage: str):
+    return [(k, v) for k in magnitude_keys(stage) for v in [()] + ([(("det", True),)] if stage == "edge_backward" else [])]
+
+
+def magnitude_case_id(key, variant) -> str:
+    return wiring_case_id(key[:9], variant) + "-" + key[9]

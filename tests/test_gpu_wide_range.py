@@ -82,3 +82,37 @@ def test_generic_activation_model_falls_back_to_its_own_wide_range_build():
 def test_pinned_f16x2_build_raises_instead_of_returning_non_finite_outputs():
     c = _run(3e5, FASTEGNN_WIDE_RANGE="0")
     assert c["raised"] and "FASTEGNN_WIDE_RANGE" in c["raised"], c
+
+
+def _max_embedding_output(golden):
+    """max |h| of the embedding on the golden's own weights and features, on the CPU in fp64 (the runner scales weight and bias: h scales with it)"""
+    import torch
+    from tests.helpers import Golden
+    g = Golden(golden)
+    p, t = g.tensors(g.params, dtype=torch.float64), g.tensors(g.inp, dtype=torch.float64)
+    h = t["node_feat"] @ p["embedding_in.weight"].T + p["embedding_in.bias"]
+    return float(h.abs().max())
+
+
+@pytest.mark.parametrize("golden", ["c16_two_graphs", "ragged3_tanh"])
+def test_range_guard_at_its_threshold(golden):
+    """The guard where only one or a few operands overflow: max |embedding output| at 0.5, 0.99, 1.01 and 2 x 65 504 (the x 3e5 runs above put
+    every hidden feature far beyond the range).  Under FASTEGNN_RANGE_CHECK=sync the call that returns must be what fp32 gives on every side of
+    the threshold -- under tanh an infinite head can come back as a finite +-1, which a check of the outputs alone would not see -- and the
+    module is on the wide-range build exactly when it said so."""
+    h_max = _max_embedding_output(golden)
+    factors = (0.5, 0.99, 1.01, 2.0)
+    scales = [f * 65504.0 / h_max for f in factors]
+    e = {k: v for k, v in os.environ.items() if k != "FASTEGNN_WIDE_RANGE"}
+    e["FASTEGNN_RANGE_CHECK"] = "sync"
+    r = subprocess.run([sys.executable, "-m", "tests.wide_range_runner", ",".join(repr(s) for s in scales), golden], cwd=ROOT, env=e,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    runs = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert [b["scale"] for b in runs] == scales
+    for f, b in zip(factors, runs):
+        print(f"{golden} max|h| = {f} x 65504: {b}")
+        assert b["raised"] is None and b["warned"] in (0, 1) and b["wide"] == bool(b["warned"]), (f, b)
+        if b["ref_finite"]:
+            assert b["finite"] and b["first_finite"] and b["err_loc"] < 1e-4, (f, b)
+            assert b["grad_finite"], (f, b)

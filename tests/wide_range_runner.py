@@ -1,7 +1,9 @@
 """Child process of tests/test_gpu_wide_range.py: one golden through the HIP module with its hidden features scaled up, under
 the library policy the environment selects (FASTEGNN_WIDE_RANGE unset / 0 / 1); prints one JSON line.
 
-    python -m tests.wide_range_runner <scale> [golden name]
+    python -m tests.wide_range_runner <scale>[,<scale>...] [golden name]
+
+Several scales: one JSON line each, in order, every one from a fresh module (a module that moved to the wide-range build stays there).
 """
 import json
 import os
@@ -16,8 +18,12 @@ if ROOT not in sys.path:
 
 
 def main():
-    scale = float(sys.argv[1])
     name = sys.argv[2] if len(sys.argv) > 2 else "c16_two_graphs"
+    for scale in sys.argv[1].split(","):
+        run(float(scale), name)
+
+
+def run(scale, name):
     from fastegnn_amd import _lib as K
     from oracle import fastegnn_ref as R
     from tests.gpu_util import model_from_golden
@@ -28,7 +34,7 @@ def main():
         m.embedding_in.weight.mul_(scale)
         m.embedding_in.bias.mul_(scale)
     kw, target, wv = g.model_kwargs(device="cuda")
-    out = dict(lib=os.path.basename(K.LIB_PATH), raised=None, warned=False)
+    out = dict(lib=os.path.basename(K.LIB_PATH), raised=None, warned=False, scale=scale)
     try:
         sync_mode = os.environ.get("FASTEGNN_RANGE_CHECK", "deferred") == "sync"
         with warnings.catch_warnings(record=True) as wlist:
@@ -66,7 +72,7 @@ def main():
             out["err_grad_max"] = max(errs.values()) if errs else None
     except FloatingPointError as e:
         out["raised"] = str(e)[:160]
-    print(json.dumps(out))
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
